@@ -2,6 +2,7 @@
 """bench.py -- megapixels/s of the Polyblur hot path on MI355X (BASELINE.json's metric).
 
     python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--mode resident|from_root]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one full polyblur_deblurring() call (n_iter=3, alpha=6, beta=1, c=0.362, b=0.468, q=0,
 method='fft', full 25-tap support) on one resident batch.  Default workload: BASELINE config 2, a single
@@ -14,14 +15,21 @@ bench.py is started directly with --gpus N > 1 (no RANK in the environment) it r
 way.  --mode resident (default, "scaling": "weak"): every rank owns its shard already (images shard with no
 data-path collective); --mode from_root: the whole batch lives on rank 0 and every step is scatter + compute
 + gather (polyblur_amd.distributed.deblur_from_root, grouped RCCL point-to-point over xGMI).  At N > 1 the
-resident run also carries a short from_root measurement in `context` (report both).  Either way
+resident run with --full also carries a short from_root measurement in `context` (report both).  Either way
 the timed region is bracketed by a barrier + device synchronise on both sides and the maximum over ranks is
 reported.
 
 Between the W warm-up steps and the K timed steps the device gets ~60 ms of the same (untimed) steps to settle its clocks
 (`settle_steps` in the line): the timed region of a 4K run is 10 ms, and without them its first steps run 5 % slow.
 
-Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
+A plain run sets up, warms up, settles, times the K steps and prints ONE JSON line (rank 0) with the contract's keys:
+`metric`, `value` (MP/s over the K timed steps), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall time of the
+timed region / K), and labels of the workload.  --dump-outputs DIR then writes what the last timed step returned as
+DIR/output.npy (DIR/output_rank<r>.npy per rank at N > 1; float32): the whole array where it has at most 2**22 / N
+elements, else the values at the flat indices np.sort(np.random.default_rng(0).integers(0, n, 2**22 // N)) -- the same
+sample in every run of the same arguments, whose inputs are seeded.
+
+--full adds everything else, each in runs of its own after the headline's.  The line then also carries
   roofline      -- the dominant kernel class (the reblurring pass), from hipEvents on the engine's stream around every
                    launch of a second, identical run of the K steps (the headline `value` is timed without them).
                    `achieved` / `frac` are SURVEY 8d's ALGORITHMIC bytes (8 words per sample and polynomial, whatever
@@ -37,6 +45,8 @@ Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
   stages_ms_per_step, context -- labelled side numbers, never the headline value; at N = 1 on the default config `context`
                    also carries the other BASELINE configs (cfg3, cfg4_share, cfg5_share: 1 warm-up + 3 timed steps each,
                    image 0 against the oracle for cfg3 / cfg4; a parity failure there fails the run too).
+  ms_per_step_device, value_at_median_step -- the K steps once more with one event between steps (median device time)
+--no-cpu-baseline, --no-context and --no-parity leave parts of --full out.
 """
 import argparse
 import json
@@ -74,10 +84,15 @@ def parse():
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--batch", type=int, default=None, help="images per GPU")
     ap.add_argument("--dtype", default=None, choices=["f32", "f16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline, per-step device times, parity against the oracle, CPU baseline and the "
+                         "labelled side measurements (off: the plain run times the headline steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/*.npy (float32; a fixed seeded sample of a large output)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-context", action="store_true",
-                    help="skip the labelled side measurements, so that a profiler sees only the headline workload's kernels")
-    ap.add_argument("--no-parity", action="store_true")
+                    help="(--full) skip the labelled side measurements, so that a profiler sees only the headline workload's kernels")
+    ap.add_argument("--no-parity", action="store_true", help="(--full) skip the parity checks against the oracle")
     ap.add_argument("--settle-ms", type=float, default=60.0,
                     help="untimed steps for this long between the warm-up and the timed region (clocks settle); 0 under a profiler, whose passes must see the same launches")
     ap.add_argument("--selftest-launcher", action="store_true",
@@ -176,6 +191,24 @@ def survey_words(opts):
     if opts.get("prefiltering"):
         words += 5.0 if opts.get("prefilter") == "domain_transform" else 2.0
     return words
+
+
+DUMP_MAX_ELEMS = 1 << 22      # float32 values written by --dump-outputs over all ranks: 16 MiB
+
+
+def dump_output(out, directory, rank, world):
+    """--dump-outputs: one step's returned array as float32 .npy -- whole, or a fixed seeded sample of its flat values."""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    name = "output.npy" if world == 1 else "output_rank%d.npy" % rank
+    cap = DUMP_MAX_ELEMS // world
+    n = out.numel()
+    if n <= cap:
+        vals = out.detach().float().cpu().numpy()
+    else:
+        idx = np.sort(np.random.default_rng(0).integers(0, n, cap))
+        vals = out.detach().reshape(-1)[torch.from_numpy(idx).to(out.device)].float().cpu().numpy()
+    np.save(os.path.join(directory, name), vals)
 
 
 def main():
@@ -293,6 +326,31 @@ def main():
     ms_per_step = 1e3 * dt / args.steps
     mp_per_step = B * H * W * world / 1e6
     value = mp_per_step / (ms_per_step / 1e3)
+    if args.dump_outputs and out is not None:                              # (from_root: only the root receives the batch)
+        dump_output(out, args.dump_outputs, rank, world)
+
+    desc = "batch=%d %dx%dx3 %s per GPU, n_iter=%d, method=fft (circular), full 25-tap support" % (
+        B, W, H, "fp32" if s == 4 else "fp16", cfg["n_iter"])
+    if cfg["opts"]:
+        desc += ", " + ", ".join("%s=%s" % kv for kv in sorted(cfg["opts"].items()))
+    headline = {
+        "metric": "megapixels/sec (n_iter=3, alpha=6, beta=1)", "value": round(value, 1), "unit": "MP/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_steps": settle_steps, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": cfg["dtype"], "data": "synthetic",
+        "config": {"workload": desc, "name": args.config, "mode": args.mode, "images_per_gpu": B, "height": H, "width": W,
+                   "parallelism": "images sharded, no data-path collective" if not from_root else
+                                  "batch on rank 0: RCCL scatter + compute + gather per step"},
+        "rccl_ranks": rccl_ranks,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
+
+    # ---- --full: everything below runs after the headline's timed steps ----------------------------------
     # the same K steps once more with an event pair around every launch: per-kernel-class device times
     if from_root:
         n_calls[0] = 0
@@ -758,24 +816,14 @@ def main():
     if side_failed:
         failed = True
 
-    desc = "batch=%d %dx%dx3 %s per GPU, n_iter=%d, method=fft (circular), full 25-tap support" % (
-        B, W, H, "fp32" if s == 4 else "fp16", cfg["n_iter"])
-    if cfg["opts"]:
-        desc += ", " + ", ".join("%s=%s" % kv for kv in sorted(cfg["opts"].items()))
-    line = {
-        "metric": "megapixels/sec (n_iter=3, alpha=6, beta=1)", "value": round(value, 1), "unit": "MP/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_steps": settle_steps, "ms_per_step": round(ms_per_step, 4),
+    line = dict(headline, **{
         "ms_per_step_device": (dict(median=round(step_ms[len(step_ms) // 2], 4), min=round(step_ms[0], 4), max=round(step_ms[-1], 4),
                                     n=len(step_ms), note="one event between steps, device time; `value` is the contract's total / K")
                                if step_ms else None),
         "value_at_median_step": (round(mp_per_step / (step_ms[len(step_ms) // 2] * 1e-3), 1) if step_ms and world == 1 else None),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": cfg["dtype"], "data": "synthetic",
-        "config": {"workload": desc, "name": args.config, "mode": args.mode, "images_per_gpu": B, "height": H, "width": W,
-                   "parallelism": "images sharded, no data-path collective" if not from_root else
-                                  "batch on rank 0: RCCL scatter + compute + gather per step"},
-        "rccl_ranks": rccl_ranks, "roofline": roofline, "parity": parity, "cpu_baseline": cpu,
+        "roofline": roofline, "parity": parity, "cpu_baseline": cpu,
         "stages_ms_per_step": stages_ms, "estimated_blur": est, "context": side, "workspace_bytes": eng.workspace_bytes(),
-    }
+    })
     print(json.dumps(line), flush=True)
     if use_dist:
         dist.barrier()
