@@ -169,7 +169,7 @@ void pb_default_options(pb_options *opt);        /* the functional API's default
  * the frequency domain inside LDS (overlap-save; same taps, same boundary models, results agree to fp32 rounding);
  * the others and rank-1 kernels keep the stencil bodies (fp32 planes: one wave per window pair, conv_wfft.hip; fp16 and
  * 8-bit planes, and passes too small to fill the chip: one workgroup per pair, conv_fft.hip).  Replaces nothing in the reference: both are
- * evaluations of filters.convolve2d (filters.py:14-49).  Environment default: PB_DENSE_EVAL=stencil | <min_phases>.
+ * evaluations of filters.convolve2d (filters.py:14-49).  This call is the only way to choose: no environment variable does.
  * (PB_STRIP=1 -- rank-1 kernels of full support through the streaming strip body, conv_strip.hip, an experiment measured
  * slower than the tile body -- exists in `python -m polyblur_amd.build --experimental` builds only; the default library
  * ignores it.  INTEGRATION.md section 5 lists every environment knob.)
@@ -179,8 +179,8 @@ void pb_default_options(pb_options *opt);        /* the functional API's default
  * three passes with the kernel's halos (pb_polyblur_batch, pb_inverse_filter, pb_time_inner_loop; per image, decided on
  * the device): same taps, same results to fp32 rounding (fewer roundings), 2 words per sample through HBM instead of 8.
  * PB_POLY1=0 in the environment switches the form off, PB_POLY1=1 restricts it to kernels within the 4-sample halo class
- * (round 3's form); PB_POLY_GAIN / PB_POLY_MIN_AREA tune the cost model (csrc/khat.h).  pb_body_selection reports the
- * choice.  All of these variables are read when the context is created. */
+ * (round 3's form); the cost model's constants are in csrc/common.h and csrc/khat.h.  pb_body_selection reports the
+ * choice.  Environment variables are read when the context is created. */
 typedef enum pb_dense_eval { PB_DENSE_STENCIL = 0, PB_DENSE_AUTO = 1 } pb_dense_eval;
 int pb_set_dense_eval(pb_ctx *ctx, int mode, int min_phases);
 /* Diagnostics: how the B images of iteration `iteration` of the most recent pb_polyblur_batch call on this context were

@@ -71,15 +71,12 @@ static int pitch4(int w) { return (w + 3) & ~3; }
 // Every environment knob of the library, read ONCE per context (pb_create) into pb_ctx -- no kernel launcher looks at the
 // environment.  They exist to compare forms on the same box (bench.py's context entries, tools/), not to configure a
 // deployment: the defaults are the product.
-//   PB_DENSE_EVAL=stencil|<n>   dense kernels never take the tile-spectrum body | from n live stencil phases on (16)
 //   PB_FFT_BODY=wg|wave         which form of the tile-spectrum body runs three-step passes (wave; fp16 temporaries --
 //                               pb_options.half_temporaries -- always take the workgroup form, the only one built for them)
 //   PB_POLY1=0..3               one-pass polynomial: 0 never, 1 4-sample halo class only, 2 + 64 x 64 windows with the
 //                               composite's halos, 3 (default) + 128 x 128 windows
-//   PB_POLY_GAIN, PB_POLY_MIN_AREA, PB_POLY_COST128, PB_POLY_MIN_PAIRS128   cost model of the forms (common.h: 0.7, 768, 8, 1)
-//   PB_ZERO_RING_ASIDE=0        ... its first two ring steps behind the window pass instead of beside it (side stream)
-//   PB_ZERO_RING_MIN_PAIRS=<n>  ... the ring form only for images of at least n three-step window pairs (4096)
 //   PB_ZERO_RING=0              method='direct' keeps three Horner steps over the whole image
+//   PB_ZERO_RING_MIN_PAIRS=<n>  ... its window pass + border ring form only for images of at least n three-step window pairs (4096)
 //   PB_TAPER_RING=0             the second and third blend of an edgetaper over the whole plane, not over the border ring
 //   PB_POLY_PADDED=0            the polynomial after an edgetaper keeps three Horner steps
 //   PB_POLY_ALWAYS=0            never PolySpec.always (issue every launch the records might need)
@@ -89,32 +86,25 @@ static int pitch4(int w) { return (w + 3) & ~3; }
 //   PB_DT_COLS_STRIP=0          the domain-transform column pass as two sweeps through global memory instead of strips
 //   PB_FFT_EXT_RADIX=0          greedy transform plans only (radices up to 16)
 //   PB_FFT_FIRST / _ROWS=0|r    the column / row transform's first and last stage: the greedy plan's order, or radix r (default: by line length)
-//   PB_FFT_LOGNB, PB_WAVE_MIN_JOBS   shapes of the column-transform / wave-body launches
 //   PB_COLS_FIXED=0, PB_ROWS_FIXED=0   the line transforms always by the run-time-plan kernels (estimate.hip), also where
 //                               lines_fixed.hip holds the plan (the tests' bit-identity reference)
-//   PB_XT=2                     the x-t approximation through two launches of the general body
-//   PB_STRIP, PB_STRIP_SEG, PB_EST_OVERLAP   measured experiments: read in --experimental builds only
-// (retired in round 6, their alternatives measured and dropped in NOTEBOOK.md: PB_ROWS_NT, PB_COLS_WIDE, PB_MAIN_STREAM_BODY,
-// PB_SIDE_STREAM, PB_SIDE_MIN_TILES -- the fields keep their defaults)
+//   PB_STRIP=1                  a measured experiment (conv_strip.hip): read in --experimental builds only
+// A knob stays while a test, bench.py or a script under tools/ names it.  Retired, their alternatives measured and dropped in
+// NOTEBOOK.md -- round 6: PB_ROWS_NT, PB_COLS_WIDE, PB_MAIN_STREAM_BODY, PB_SIDE_STREAM, PB_SIDE_MIN_TILES; after it, with their
+// fields and branches: PB_POLY_GAIN, PB_POLY_MIN_AREA, PB_POLY_COST128 (constants of common.h), PB_POLY_MIN_PAIRS128,
+// PB_ZERO_RING_ASIDE, PB_WAVE_MIN_JOBS, PB_FFT_LOGNB, PB_XT, PB_STRIP_SEG, PB_EST_OVERLAP, PB_DENSE_EVAL (pb_set_dense_eval is
+// the interface)
 static void pb_read_knobs(pb_ctx *ctx) {
     auto geti = [](const char *n, int &v) { if (const char *e = getenv(n)) v = atoi(e); };
     auto getl = [](const char *n, long &v) { if (const char *e = getenv(n)) v = atol(e); };
-    auto getf = [](const char *n, float &v) { if (const char *e = getenv(n)) v = (float)atof(e); };
-    if (const char *e = getenv("PB_DENSE_EVAL")) {
-        if (e[0] == 's') ctx->fft_min_phases = -1;
-        else if (e[0] >= '0' && e[0] <= '9') ctx->fft_min_phases = atoi(e);
-    }
     if (const char *e = getenv("PB_FFT_BODY")) ctx->fft_wave = (e[0] == 'w' && e[1] == 'g') ? 0 : 1;
-    if (const char *e = getenv("PB_XT")) ctx->xt_two_launch = e[0] == '2';
 #ifdef PB_EXPERIMENTAL
-    geti("PB_STRIP", ctx->strip_mode); geti("PB_STRIP_SEG", ctx->strip_seg);
+    geti("PB_STRIP", ctx->strip_mode);
 #endif
     geti("PB_EST_GRAY_ROWS", ctx->est_gray_rows); geti("PB_EST_LEAN", ctx->est_lean); geti("PB_DT_ROWS_REG", ctx->dt_rows_reg); geti("PB_DT_COLS_STRIP", ctx->dt_cols_strip); geti("PB_DT_COLS_COOP", ctx->dt_cols_coop);
-    geti("PB_FFT_EXT_RADIX", ctx->fft_ext_radix); geti("PB_FFT_FIRST", ctx->fft_first); geti("PB_FFT_FIRST_ROWS", ctx->fft_first_rows); geti("PB_FFT_LOGNB", ctx->fft_lognb); geti("PB_COLS_FIXED", ctx->cols_fixed); geti("PB_ROWS_FIXED", ctx->rows_fixed);
-    getl("PB_WAVE_MIN_JOBS", ctx->wave_min_jobs);
-    geti("PB_POLY1", ctx->poly_mode); getf("PB_POLY_GAIN", ctx->poly_gain); geti("PB_POLY_MIN_AREA", ctx->poly_min_area);
-    getf("PB_POLY_COST128", ctx->poly_cost128); getl("PB_POLY_MIN_PAIRS128", ctx->poly_min_pairs128);
-    geti("PB_POLY_ALWAYS", ctx->poly_always); geti("PB_POLY_PADDED", ctx->poly_padded); geti("PB_TAPER_RING", ctx->taper_ring); geti("PB_ZERO_RING", ctx->zero_ring); getl("PB_ZERO_RING_MIN_PAIRS", ctx->zero_ring_min_pairs); geti("PB_ZERO_RING_ASIDE", ctx->zero_ring_aside);
+    geti("PB_FFT_EXT_RADIX", ctx->fft_ext_radix); geti("PB_FFT_FIRST", ctx->fft_first); geti("PB_FFT_FIRST_ROWS", ctx->fft_first_rows); geti("PB_COLS_FIXED", ctx->cols_fixed); geti("PB_ROWS_FIXED", ctx->rows_fixed);
+    geti("PB_POLY1", ctx->poly_mode);
+    geti("PB_POLY_ALWAYS", ctx->poly_always); geti("PB_POLY_PADDED", ctx->poly_padded); geti("PB_TAPER_RING", ctx->taper_ring); geti("PB_ZERO_RING", ctx->zero_ring); getl("PB_ZERO_RING_MIN_PAIRS", ctx->zero_ring_min_pairs);
 }
 
 extern "C" {
@@ -159,7 +149,7 @@ int pb_set_dense_eval(pb_ctx *ctx, int mode, int min_phases) {
     if (!ctx || (mode != PB_DENSE_STENCIL && mode != PB_DENSE_AUTO) || min_phases < 0 || min_phases > PB_MAX_PHASES + 1)
         return PB_ERR_BADARG;
     ctx->fft_min_phases = mode == PB_DENSE_STENCIL ? -1 : min_phases;
-    pb_forget_records(ctx, nullptr, 0);
+    pb_forget_hints(ctx);                                 // (which bodies the cached records take has changed; flip_sets have not)
     return PB_OK;
 }
 
@@ -229,23 +219,14 @@ int pb_malloc(pb_ctx *ctx, void **dptr, size_t bytes) {
 }
 int pb_free(pb_ctx *ctx, void *dptr) {
     if (!ctx) return PB_ERR_BADARG;
-    {
-        // what the context has cached about records is a hint and goes wholesale; which caller-supplied record sets hold taps that
-        // are not point-symmetric is not (common.h: FlipSet): only the sets inside the allocation being freed are dropped
-        auto keep = std::move(ctx->flip_sets);
-        pb_forget_records(ctx, nullptr, 0);
-        hipDeviceptr_t base = nullptr; size_t size = 0;
-        if (dptr && hipMemGetAddressRange(&base, &size, dptr) == hipSuccess) {
-            const char *lo = static_cast<const char *>(static_cast<void *>(base)), *hi = lo + size;
-            for (auto it = keep.begin(); it != keep.end();) {
-                const char *a = static_cast<const char *>(it->first);
-                if (a >= lo && a < hi) it = keep.erase(it); else ++it;
-            }
-        } else {
-            (void)hipGetLastError();
-            keep.erase(dptr);
-        }
-        ctx->flip_sets = std::move(keep);
+    // what the context has cached about records is a hint and goes wholesale; which caller-supplied record sets hold taps that
+    // are not point-symmetric is not (common.h: FlipSet): only the sets inside the allocation being freed are dropped
+    pb_forget_hints(ctx);
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (dptr && hipMemGetAddressRange(&base, &size, dptr) == hipSuccess) pb_forget_range(ctx, base, size);
+    else {
+        (void)hipGetLastError();
+        ctx->flip_sets.erase(dptr);
     }
     PB_HIP(hipStreamSynchronize(ctx->stream));
     PB_HIP(hipFree(dptr));
@@ -404,19 +385,13 @@ PolySpec poly_spec(pb_ctx *ctx, const ConvPass *steps, float alpha, float beta, 
         }
         return no_poly();
     }
-    // (128 x 128 windows need an image of some size: a workgroup takes ~38 us for its pair whatever the launch, and a 700 x 500
-    // image yields 72 of them for 256 CUs -- 0.35 against 0.32 ms per call.  The rule looks at ONE image, not at the batch, so
-    // that what an image gets does not depend on the batch it travels in; the threshold sits just below 1080p x 3 channels
-    // (396 pairs at 90 x 90 tiles: alone 4 % slower through 128 x 128 windows, in a batch of 32 10 % faster))
-    const long pairs128 = (long)((steps[2].W + 179) / 180) * ((steps[2].H + 89) / 90) * steps[2].C;
-    const float cost128 = pairs128 >= ctx->poly_min_pairs128 ? ctx->poly_cost128 : 0.f;
     // (every composite of a 25-tap kernel fits a 128 x 128 window -- halo <= 36, tile >= 56 -- so where those windows are admitted
     // and every kernel is the estimation's own Gaussian, "every image takes one window pass" is a fact of the call's options and
     // sizes: PolySpec.always, and pb_launch_conv_poly issues the two window launches only)
-    const int always = (mode == 3 && cost128 > 0.f && gaussians && ctx->poly_always) ? 1 : 0;
+    const int always = (mode == 3 && gaussians && ctx->poly_always) ? 1 : 0;
     // (under the zero boundary only that class takes one pass: interior by the window pass, frame by three ring steps)
     if (steps[0].boundary != PB_WRAP && !always) return no_poly();
-    return PolySpec{mode, alpha / 2 - beta + 2, 3 * beta - alpha - 6, 5 - 3 * beta + alpha / 2, beta, ctx->poly_gain, ctx->poly_min_area, cost128, always};
+    return PolySpec{mode, alpha / 2 - beta + 2, 3 * beta - alpha - 6, 5 - 3 * beta + alpha / 2, beta, PB_POLY_GAIN, PB_POLY_MIN_AREA, PB_POLY_COST128, always};
 }
 
 // y = a3 K^3 x + a2 K^2 x + a1 K x + beta x by Horner, three stencil passes (deblurring.py:122-138).
@@ -426,10 +401,9 @@ int run_polynomial(pb_ctx *ctx, const Geometry &g, const void *xsrc, int x_dtype
                    int dst_dtype, int clamp01) {
     const float a3 = alpha / 2 - beta + 2, a2 = 3 * beta - alpha - 6, a1 = 5 - 3 * beta + alpha / 2;
     if (g.sep1) {
-        // K ~= K2 after K1 (estimate.hip: sep_records_kernel).  One launch per step keeps u = K1 * t in LDS (conv_xt.hip);
-        // dtype combinations it is not built for (8-bit images) -- or PB_XT=2 -- take two launches through the sparse
+        // K ~= K2 after K1 (estimate.hip: sep_records_kernel).  One launch per step keeps u = K1 * t in LDS (conv_xt.hip, the
+        // --experimental build); where it is not built -- the default build, 8-bit images -- two launches through the sparse
         // phase lists of the general body: u = K1 * t, then t' = scale (K2 * u) + coef x
-        const bool two_launch = ctx->xt_two_launch != 0;
         const float scale[3] = {a3, 1.f, 1.f}, coef[3] = {a2, a1, beta};
         float *tmp[2] = {t1, t2};
         ConvPass p1 = base_pass(g, g.sep1, boundary), p2 = base_pass(g, g.sep2, boundary);
@@ -438,18 +412,15 @@ int run_polynomial(pb_ctx *ctx, const Geometry &g, const void *xsrc, int x_dtype
         for (int step = 0; step < 3; ++step) {
             if (step < 2) set_out_padded(p2, g, tmp[step]); else set_out_interior(p2, g, dst, dst_dtype);
             p2.scale = scale[step]; p2.coef = coef[step]; p2.clamp01 = step == 2 ? clamp01 : 0;
-            int rc = PB_ERR_UNSUPPORTED;
-            if (!two_launch) {
-                if (step == 0) set_in_virtual(p2, g, xsrc, x_dtype); else set_in_padded(p2, g, tmp[step - 1]);
-                rc = pb_launch_conv_xt(ctx, p2);
-                if (rc != PB_OK && rc != PB_ERR_UNSUPPORTED) return rc;
-                if (rc == PB_OK) {
-                    // images whose exact kernel is rank-1 were skipped there: the exact separable body does them
-                    ConvPass pe = p2;
-                    pe.info = info; pe.skip_general = 1;
-                    rc = pb_launch_conv(ctx, pe);
-                    if (rc) return rc;
-                }
+            if (step == 0) set_in_virtual(p2, g, xsrc, x_dtype); else set_in_padded(p2, g, tmp[step - 1]);
+            int rc = pb_launch_conv_xt(ctx, p2);
+            if (rc != PB_OK && rc != PB_ERR_UNSUPPORTED) return rc;
+            if (rc == PB_OK) {
+                // images whose exact kernel is rank-1 were skipped there: the exact separable body does them
+                ConvPass pe = p2;
+                pe.info = info; pe.skip_general = 1;
+                rc = pb_launch_conv(ctx, pe);
+                if (rc) return rc;
             }
             if (rc == PB_ERR_UNSUPPORTED) {
                 if (step == 0) set_in_virtual(p1, g, xsrc, x_dtype); else set_in_padded(p1, g, tmp[step - 1]);
@@ -474,7 +445,7 @@ int run_polynomial(pb_ctx *ctx, const Geometry &g, const void *xsrc, int x_dtype
     // (under the wrap boundary the three steps are one filter, deblurring.py:139-169: images for which one window pass
     // with that filter's spectrum is the cheaper form take it, pb_fft_sel.poly; the spectra are then the polynomial's)
     // (records the estimation has just built under PolySpec.always keep that spec: their spectra are already those it asks for)
-    const bool by_est = ctx->khat_by_estimate && ctx->khat_owner == info && ctx->khat_B == g.B && ctx->poly_built.always;
+    const bool by_est = ctx->spectra.spec().always && ctx->spectra.by_estimate() && ctx->spectra.holds(info, g.B);
     ctx->poly_want = poly_spec(ctx, steps, alpha, beta, by_est || g.est_gaussians);
     const int rc = pb_launch_conv_poly(ctx, steps);
     ctx->poly_want = no_poly();

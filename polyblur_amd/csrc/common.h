@@ -68,6 +68,37 @@ inline bool same_spec(const PolySpec &x, const PolySpec &y) {
 // the image's three Horner steps, whose launches skip it.
 struct pb_fft_sel { int use_fft; int rf; int strip; int poly; int hx; int hy; int pad_[2]; };
 
+// What one scratch set of spectra + selections holds: the records they were built from (`n` of them at `owner`), the PolySpec
+// they were built under, the slot of the selection scratch they were written to, whether the estimation built them (beside
+// the records, on the stream: nothing to read back) and the buffer they were built into.  A hint: dropping it costs one
+// khat_kernel launch.  The questions and updates the launchers need are the members; nothing else reads the fields.
+struct SpectraSet {
+    bool holds(const void *info, int B) const { return owner && owner == info && n == B; }
+    // (same_spec compares `always` too: the kernels' own spectra under always == 2 are not those under always == 0)
+    bool holds(const void *info, int B, const PolySpec &s) const { return holds(info, B) && same_spec(built, s); }
+    void claim(const void *info, int B, const PolySpec &s, int sel_slot, bool by_estimate) {
+        owner = info; n = B; built = s; slot_ = sel_slot; est = by_estimate;
+    }
+    void drop() { owner = nullptr; n = 0; est = false; }
+    // a write into [lo, hi): a run of records that overlaps it anywhere, not only at its first record
+    void drop_if_overlaps(const void *lo, const void *hi) {
+        const char *o = static_cast<const char *>(owner);
+        if (o && o < static_cast<const char *>(hi) && static_cast<const char *>(lo) < o + sizeof(pb_blur_info) * (size_t)n) drop();
+    }
+    void rebind(const void *b) { if (b != buf) { buf = b; drop(); } }      // (the scratch buffer was reallocated)
+    bool built_into(const void *b) const { return b && b == buf; }
+    bool by_estimate() const { return est; }
+    int slot() const { return slot_; }
+    const PolySpec &spec() const { return built; }
+private:
+    const void *owner = nullptr;         // nullptr: unknown
+    int n = 0;                           // (a longer run at the same address has stale tails)
+    PolySpec built = no_poly();
+    int slot_ = 0;
+    bool est = false;
+    const void *buf = nullptr;
+};
+
 struct pb_ctx {
     bool prof_on = false;
     std::vector<ProfRec> prof;
@@ -86,7 +117,7 @@ struct pb_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     size_t est_done_bytes = 0;     // size of the zero-initialised arrival counters
     // dense (non rank-1) kernels with at least this many live stencil phases are evaluated per tile in the frequency
-    // domain (conv_fft.hip) instead of by the stencil body; < 0: never (pb_set_dense_eval, env PB_DENSE_EVAL)
+    // domain (conv_fft.hip) instead of by the stencil body; < 0: never (pb_set_dense_eval)
     int fft_min_phases = 16;
     // which tile-spectrum body evaluates them: 1 = one wave per window pair (conv_wfft.hip), 0 = one workgroup per
     // window pair (conv_fft.hip); env PB_FFT_BODY=wg|wave
@@ -110,13 +141,9 @@ struct pb_ctx {
     std::map<const void *, FlipSet> flip_sets;
     int sel_slot = 0, sel_last = 0, sel_B = 0;           // "conv.fftsel" holds PB_SEL_SLOTS runs of sel_B records: the slot passes write to / read from
     const std::vector<pb_fft_sel> *known_sel = nullptr;   // the records of the pass being launched, where the host has them (sizes its job grid)
-    const void *khat_owner = nullptr;    // record set whose spectra "conv.khat" holds (nullptr: unknown)
-    int khat_slot = 0;                   // ... and the slot of "conv.fftsel" their selections were written to
-    int khat_B = 0;                      // ... and how many of its records they cover (a longer run at the same address has stale tails)
-    const void *khat_buf = nullptr;
-    bool khat_by_estimate = false;
-    // one-pass polynomial experiment (env PB_POLY1=1): what the spectra in "conv.khat" were built for, and what the call
-    // in progress wants (set around the estimation / the polynomial; off for every other pass)
+    SpectraSet spectra;                  // what "conv.khat" / "conv.fftsel" hold
+    // one-pass polynomial (env PB_POLY1): poly_want = what the call in progress wants the spectra to be those of (set around
+    // the estimation / the polynomial; off for every other pass)
     // 0 never; 1 every eligible polynomial, host-built records included (those are then not cached); 2 (default) the
     // pipeline's: mildly blurred images -- the method's own use case -- estimate kernels like sigma 0.6 / rho 0.3 at an
     // oblique angle or the clamped isotropic 0.3 / 0.3, within the 4-sample halo (under the adaptive policy; the latter
@@ -125,32 +152,16 @@ struct pb_ctx {
     // qualifies; otherwise a composite launch is needed, which finds no work then and costs 1 % of a 4K call even on the
     // side stream (1.182 -> 1.195 ms): issued under the adaptive policy only.
     int poly_mode = 3;
-    PolySpec poly_built = no_poly(), poly_want = no_poly();
+    PolySpec poly_want = no_poly();
     // A SECOND set of spectra + selections ("conv.khat2" / "conv.fftsel2"), built by the estimation beside the first where the
     // call will need both -- the zero boundary's ring steps want the kernels' own spectra next to the polynomial's, the
     // polynomial behind an edgetaper wants its own next to the kernels' -- instead of by a khat_kernel launch of its own
     // between the estimation and the pass (measured: 23 us per iteration of a 4K method='direct' call, 9 us with edgetaping).
     // poly_want2: what the estimation in progress is asked to build there (on == 0 && always == 0: nothing).
-    PolySpec poly_want2 = no_poly(), khat2_spec = no_poly();
-    const void *khat2_owner = nullptr;   // record set whose spectra the second set holds (nullptr: none)
-    int khat2_B = 0;
-    const void *khat2_buf = nullptr;
+    PolySpec poly_want2 = no_poly();
+    SpectraSet spectra2;
     unsigned sel2_mask = 0;              // iterations (slots of "conv.fftsel2", as of "conv.fftsel") whose polynomial read the SECOND set's selections: pb_body_selection reports those
-    // cost model of the general one-pass form (PolySpec.on == 2; env PB_POLY_GAIN, PB_POLY_MIN_AREA): an image takes it when
-    // its composite tile has at least poly_min_area samples and -- an image that would otherwise take three tile-spectrum
-    // passes -- 3 x that area is at least poly_gain x the tile area of its three-step windows (cost per output sample, in
-    // window pairs: 3 / (poly_gain x three-step tile area) against 1 / composite tile area).  A Horner step costs more than a
-    // one-pass window of the same tile -- the x operand, 8 words per sample instead of 2, two launches more: measured 0.254 ms
-    // for three steps at 40 x 40 tiles against 0.153 ms for one pass on 128 x 128 windows at 64 x 68 tiles (4K), 0.092 against
-    // 0.050 at 1080p -- hence 0.7 (swept on 32 x 1080p: 1.0 -> 6.61, 0.85 -> 6.26, 0.7 -> 6.14, 0.6 -> 6.15 ms per step); one
-    // pass over 768-sample tiles takes what three rank-1 stencil passes take
-    float poly_gain = 0.7f;
-    int poly_min_area = 768;
-    long poly_min_pairs128 = 1;          // env PB_POLY_MIN_PAIRS128: 128 x 128 windows only for images of at least this many window pairs (at 90 x 90 tiles, all channels).  150 in round 4 (a 700 x 500 image was slower with them: 0.256 -> 0.279 ms); 1 since the one-pass class removed the other launches (round 5, same box: 700 x 500 0.242 -> 0.211 ms per call, 256 x 256 0.222 -> 0.192, 1080p gray 0.431 -> 0.319, 16 x 700 x 500 1.14 -> 0.72): every size is in the class
-    float poly_cost128 = 8.0f;           // env PB_POLY_COST128; <= 0: never 128 x 128 windows.  Measured at 4K: a 128 x 128 pair costs 6 - 6.5 pairs of
-                                         // 64 x 64 with host-built records, and a launch of its own (~10 us) in the pipeline
-    int zero_ring_aside = 1;             // env PB_ZERO_RING_ASIDE: 0 = the ring steps of a zero-boundary polynomial all behind its window pass on the caller's stream
-    long zero_ring_min_pairs = 4096;     // env PB_ZERO_RING_MIN_PAIRS: ... only for images of at least this many three-step window pairs (40 x 40 tiles, all channels: two rounds of the chip)
+    long zero_ring_min_pairs = 4096;     // env PB_ZERO_RING_MIN_PAIRS: the window pass + border ring form of a zero-boundary polynomial only for images of at least this many three-step window pairs (40 x 40 tiles, all channels: two rounds of the chip)
     int zero_ring = 1;                   // env PB_ZERO_RING: 0 = a polynomial under the zero boundary (method='direct') keeps three Horner steps over the whole image
     int taper_ring = 1;                  // env PB_TAPER_RING: 0 = every blend of an edgetaper covers the whole padded plane
     int poly_padded = 1;                 // env PB_POLY_PADDED: 0 = a polynomial whose operand is a padded plane (after an edgetaper) keeps three Horner steps
@@ -159,22 +170,13 @@ struct pb_ctx {
     int dt_cols_coop = 1;                // env PB_DT_COLS_COOP: 0 = never the few-columns form of the column pass (dt_cols_coop_kernel), 2 = always where it applies
     int dt_rows_reg = 1;                 // env PB_DT_ROWS_REG: 0 = the domain-transform row pass always through global memory (dt_rows_fused_kernel), 2 = registers, one wave per row always, 3 = a row over four waves always (dt_rows_regw_kernel)
     int poly_always = 1;                 // env PB_POLY_ALWAYS: 0 = never PolySpec.always (every polynomial issues all the launches its records might need)
-    long side_min_tiles = 12288;         // (PB_SIDE_MIN_TILES until round 6) stencil tiles per launch from which the launches that may find no work go to the side stream
-    int main_stream_body = -1;           // (PB_MAIN_STREAM_BODY until round 6) which launch stays on the caller's stream when the others go to the side stream (0 = wave body, 1 = 128 x 128; -1 = by spec)
     int est_gray_rows = 1;               // env PB_EST_GRAY_ROWS: 1 = gray + range + row transform in one launch where measured faster (fp32 planes, lines of up to 4096 samples), 2 = for any line held in LDS, 0 = never
     int fft_ext_radix = 1;               // env PB_FFT_EXT_RADIX: 0 = greedy plans only (radices up to 16)
     int fft_first_rows = -1;             // env PB_FFT_FIRST_ROWS: the same for the row transforms (rows_plan)
     int fft_first = -1;                  // env PB_FFT_FIRST: the radix of the column transform's first / last stage where the plan holds it; 0 = the plan's own order; -1 = chosen by trips (launch_cols)
     // tuning / comparison knobs of single kernels, read once in pb_create (the table of every knob: api.hip, pb_read_knobs)
-    long wave_min_jobs = 0;              // env PB_WAVE_MIN_JOBS: three-step passes of fewer window pairs than this go to the workgroup form of the tile-spectrum body
-    int fft_lognb = -1;                  // env PB_FFT_LOGNB: log2 of the complex lines per column workgroup (-1: by LDS size)
-    int rows_fixed = 1;                  // env PB_ROWS_FIXED: the same for the row transforms (gray_rows_kernel / grad_rows_kernel)
     int cols_fixed = 1;                  // env PB_COLS_FIXED: 0 = the column transform always by the run-time-plan kernel (grad_cols_kernel), also where lines_fixed.hip holds the plan
-    int cols_wide = 1;                   // (PB_COLS_WIDE until round 6) 0 = never the double-width column tile
-    int rows_nt = 0;                     // (PB_ROWS_NT until round 6) threads per row workgroup (128 / 256 / 512; 0 = by line length and grid size)
-    int xt_two_launch = 0;               // env PB_XT=2: the x-t approximation as two launches of the general body
-    int est_overlap = -1;                // env PB_EST_OVERLAP (--experimental builds): rows and columns side by side on two streams
-    int strip_seg = 0;                   // env PB_STRIP_SEG (--experimental builds): segment height of the strip body
+    int rows_fixed = 1;                  // env PB_ROWS_FIXED: the same for the row transforms (gray_rows_kernel / grad_rows_kernel)
     int strip_mode = 0;                  // env PB_STRIP: 1 = rank-1 kernels of full support take the streaming strip body (fp32 planes; --experimental builds only)
 };
 
@@ -236,6 +238,10 @@ constexpr int PB_SEL_SLOTS = 16;
 constexpr int PB_KHAT_STRIDE = 128 * 128;                  // floats of spectrum per image in "conv.khat": 64 x 64 of them, or 128 x 128 (one pass on 128 x 128 windows)
 constexpr int PB_POLY128_MIN_T = 56;                       // smallest tile side of a one-pass 128 x 128 window (bounds the job grid): composite halos up to 36 = 3 x 12, every composite there is
 constexpr int PB_POLY_MIN_TX = 24, PB_POLY_MIN_TY = 16;     // smallest tile of a one-pass window (bounds the job grid)
+// cost model of the one-pass forms (khat.h; the sweeps: NOTEBOOK.md), what PolySpec.gain / min_area / cost128 are filled from
+constexpr float PB_POLY_GAIN = 0.7f;                       // a Horner step costs more than a one-pass window of the same tile (x operand, two launches more)
+constexpr int PB_POLY_MIN_AREA = 768;                      // one pass over 768-sample tiles takes what three rank-1 stencil passes take
+constexpr float PB_POLY_COST128 = 8.0f;                    // a 128 x 128 window pair in pairs of 64 x 64 (measured 6 - 6.5 at 4K, plus a launch of its own in the pipeline)
 
 
 struct ConvPass {
@@ -281,11 +287,12 @@ int pb_khat2_buffers(pb_ctx *ctx, int B, float **khat, pb_fft_sel **sel);  // ..
 // the spec under which the spectra a pass reads were built: the second set's where the pass reads that set (the polynomial behind
 // an edgetaper, whose FIRST set holds the blends' kernels -- job lists sized from the first set's spec were too short there)
 inline const PolySpec &pb_spec_of_spectra(const pb_ctx *ctx, const void *khat) {
-    return khat && khat == ctx->khat2_buf ? ctx->khat2_spec : ctx->poly_built;
+    return ctx->spectra2.built_into(khat) ? ctx->spectra2.spec() : ctx->spectra.spec();
 }
 int pb_cache_records(pb_ctx *ctx, const pb_blur_info *info, int B);        // conv.hip: after the host (re)built these records
-void pb_forget_records(pb_ctx *ctx, const void *info, int B);                 // B records at info are about to be rewritten; nullptr: all
-void pb_forget_range(pb_ctx *ctx, const void *dst, size_t bytes);            // a host write into device memory
+void pb_forget_range(pb_ctx *ctx, const void *dst, size_t bytes);            // a write into device memory: every fact and hint about records it overlaps
+inline void pb_forget_records(pb_ctx *ctx, const void *info, int B) { pb_forget_range(ctx, info, sizeof(pb_blur_info) * (size_t)B); }   // B records at info are about to be rewritten
+void pb_forget_hints(pb_ctx *ctx);                                           // the record cache and both spectra sets (flip_sets are facts: by range only)
 int pb_launch_conv_fft(pb_ctx *ctx, const ConvPass &p);
 int pb_launch_conv_strip(pb_ctx *ctx, const ConvPass &p);                    // conv_strip.hip; PB_ERR_UNSUPPORTED: not an all-fp32 plain Horner pass
 int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p);                     // conv_wfft.hip; PB_ERR_UNSUPPORTED: dtype combination not built
@@ -293,7 +300,7 @@ bool pb_conv_fft_types(const ConvPass &p);                                   // 
 bool pb_conv_wfft_types(const ConvPass &p);
 int pb_launch_conv_w128(pb_ctx *ctx, const ConvPass &p);                     // conv_w128.hip: the one-pass polynomial on 128 x 128 windows (pb_fft_sel.poly == 2)
 bool pb_conv_w128_feasible(const ConvPass &p);                               // ... and whether its worst-case job list fits the grid
-bool pb_conv_wfft_feasible(const ConvPass &p, bool poly2, int min_area);     // conv_wfft.hip: likewise for the wave form
+bool pb_conv_wfft_feasible(const ConvPass &p, bool poly2);                   // conv_wfft.hip: likewise for the wave form
 bool pb_conv_w128_types(int in_dtype, int out_dtype);                                  // ... whether it is built for the pass's types
 bool pb_poly_three_steps_ok(pb_ctx *ctx, const ConvPass *steps);             // conv.hip: the three steps can all take the wave form (PolySpec.always == 2)
 int pb_poly_spec_mode(pb_ctx *ctx, const ConvPass *steps);                   // conv.hip: the PolySpec.on a polynomial with these steps may ask for

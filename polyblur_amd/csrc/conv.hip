@@ -369,12 +369,12 @@ int pb_launch_conv(pb_ctx *ctx, const ConvPass &p0) {
     if (fft || (have && ctx->poly_want.on)) {
         float *k = nullptr; pb_fft_sel *s = nullptr;
         // (spectra an earlier pass built count only while the scratch still holds them for these records)
-        const bool built = (p.khat_ready || have || ctx->khat_by_estimate) && ctx->khat_owner == p.info && ctx->khat_B == B;   // (pb_build_khat also rebuilds spectra of another PolySpec)
+        const bool built = (p.khat_ready || have || ctx->spectra.by_estimate()) && ctx->spectra.holds(p.info, B);   // (pb_build_khat also rebuilds spectra of another PolySpec)
         const int rc = pb_build_khat(ctx, p.info, B, &k, &s, !built);
         if (rc) return rc;
         p.khat = k; p.fsel = s;      // (the stencil bodies read the selection too: they skip the one-pass images)
     } else if (!p.khat_ready && !have) {
-        ctx->khat_owner = nullptr; ctx->khat_B = 0;     // device-built records took a pass without spectra: whatever the scratch holds is not theirs
+        ctx->spectra.drop();     // device-built records took a pass without spectra: whatever the scratch holds is not theirs
     }
     // rank-1 kernels of full support on fp32 planes: the streaming strip body (host-built records only: with device-built
     // ones it would be one more launch that usually finds no work)
@@ -394,7 +394,7 @@ int pb_launch_conv(pb_ctx *ctx, const ConvPass &p0) {
 #endif
     // (PolySpec.always == 2, records of the estimation: every image takes the window form -- no stencil launch to find that out)
     const bool windows_only = !have && fft && !ctx->poly_want.on && ctx->poly_want.always == 2 && ctx->fft_wave && pb_conv_wfft_types(p) &&
-                              pb_conv_wfft_feasible(p, false, ctx->poly_min_area);
+                              pb_conv_wfft_feasible(p, false);
     const bool tile_needed = windows_only ? false : (!have || (strip_done ? kf->any_tile : kf->any_other));
     if (tile_needed) {
         const int rc = launch_stencil(ctx, p);
@@ -446,6 +446,8 @@ int pb_poly_spec_mode(pb_ctx *ctx, const ConvPass *steps) {
     if (steps[0].in_kind != SRC_VIRTUAL && !ctx->poly_padded) return 0;
     // who runs the one pass: the first step's launch where it stores the type the last step stores (ConvPass.poly = 2), else
     // a composite launch from the first step's input to the last step's output -- whose types must be built
+    // (priced on the first step's PADDED output extent, not on the composite pass's crop: where the first step's launch
+    // takes the one-pass images along, ITS job list is the one that must fit)
     ConvPass pc = steps[0];
     pc.out_dtype = steps[2].out_dtype;
     const bool fold = steps[0].out_dtype == steps[2].out_dtype;
@@ -453,8 +455,8 @@ int pb_poly_spec_mode(pb_ctx *ctx, const ConvPass *steps) {
     for (int s = 0; s < 3; ++s) wave = wave && pb_conv_wfft_types(steps[s]);
     // (job lists sized for the smallest one-pass tiles must fit the grid: a batch too large for them keeps the forms whose
     // lists are shorter -- three Horner steps in the end -- instead of failing the call)
-    if (wave && !pb_conv_wfft_feasible(pc, true, ctx->poly_min_area)) wave = false;
-    if (wave) return (ctx->poly_mode >= 3 && ctx->poly_cost128 > 0.f && pb_conv_w128_types(pc.in_dtype, pc.out_dtype) &&
+    if (wave && !pb_conv_wfft_feasible(pc, true)) wave = false;
+    if (wave) return (ctx->poly_mode >= 3 && pb_conv_w128_types(pc.in_dtype, pc.out_dtype) &&
                       pb_conv_w128_feasible(pc)) ? 3 : 2;
     return (fold || pb_conv_fft_types(pc)) ? 1 : 0;
 }
@@ -463,10 +465,42 @@ int pb_poly_spec_mode(pb_ctx *ctx, const ConvPass *steps) {
 bool pb_poly_three_steps_ok(pb_ctx *ctx, const ConvPass *steps) {
     if (ctx->poly_mode == 0 || ctx->fft_min_phases < 0 || !ctx->fft_wave) return false;
     for (int s = 0; s < 3; ++s)
-        if (steps[s].epilogue != EPI_HORNER || !fft_pass_ok(steps[s]) || !pb_conv_wfft_types(steps[s]) || !pb_conv_wfft_feasible(steps[s], false, ctx->poly_min_area))
+        if (steps[s].epilogue != EPI_HORNER || !fft_pass_ok(steps[s]) || !pb_conv_wfft_types(steps[s]) || !pb_conv_wfft_feasible(steps[s], false))
             return false;
     return true;
 }
+
+// The one window pass of a polynomial: from the first step's input to the last step's output (ConvPass.poly = 1).
+static ConvPass composite_pass(const ConvPass *steps) {
+    ConvPass pc = steps[0];
+    pc.out = steps[2].out; pc.out_kind = steps[2].out_kind; pc.out_dtype = steps[2].out_dtype;
+    pc.out_pitch = steps[2].out_pitch; pc.out_plane = steps[2].out_plane;
+    pc.scale = 1.f; pc.coef = 0.f; pc.clamp01 = steps[2].clamp01; pc.poly = 1;
+    return pc;
+}
+
+// The context's side stream inside one polynomial.  Construction forks it behind what the caller's stream holds so far
+// (`forked`: whether that worked); run() issues a callable's launches on it and records where they end; join() makes the
+// caller's stream wait for that point -- on every way out once the fork has happened: later calls share the scratch planes.
+struct SideStream {
+    pb_ctx *ctx;
+    hipStream_t main;
+    hipError_t forked, recorded = hipErrorNotReady;
+    explicit SideStream(pb_ctx *c) : ctx(c), main(c->stream) {
+        forked = hipEventRecord(ctx->ev_fork, main);
+        if (forked == hipSuccess) forked = hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0);
+    }
+    template <typename F> int run(F &&launches) {
+        ctx->stream = ctx->aux;
+        const int rc = launches();
+        ctx->stream = main;
+        recorded = hipEventRecord(ctx->ev_join, ctx->aux);       // (before the caller's stream gets its own launches, as ever)
+        return rc;
+    }
+    hipError_t join() {
+        return recorded != hipSuccess ? recorded : hipStreamWaitEvent(main, ctx->ev_join, 0);      // (a failed record skips the wait)
+    }
+};
 
 // The three Horner steps of one polynomial.  Whether the tile-spectrum body may be used is decided ONCE, from all three
 // geometries (a body decided per step could meet spectra no earlier step had built); its spectra are built by the first
@@ -480,16 +514,17 @@ bool pb_poly_three_steps_ok(pb_ctx *ctx, const ConvPass *steps) {
 int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
     bool fft = ctx->fft_min_phases >= 0;
     for (int s = 0; s < 3; ++s) fft = fft && fft_pass_ok(steps[s]);
+    const pb_blur_info *info = steps[0].info;
     const int B = steps[0].P / steps[0].C;
     // Records the host built (pb_make_kernels / pb_set_kernels) meeting a one-pass spec for the first time: the spectra of
     // that spec are built and the device's choice read back now -- one synchronisation per record set and spec -- so that
     // every later polynomial on them issues exactly the launches it needs, with job grids of exactly the size it needs.
     {
-        const auto known = ctx->rec_cache.find(steps[0].info);
+        const auto known = ctx->rec_cache.find(info);
         if (fft && ctx->poly_want.on && known != ctx->rec_cache.end() && known->second.B == B &&
             !(known->second.poly_valid && same_spec(known->second.spec, ctx->poly_want))) {
             float *k0 = nullptr; pb_fft_sel *s0 = nullptr;
-            int rc0 = pb_build_khat(ctx, steps[0].info, B, &k0, &s0, true);
+            int rc0 = pb_build_khat(ctx, info, B, &k0, &s0, true);
             if (rc0) return rc0;
             std::vector<pb_fft_sel> h((size_t)B);
             PB_HIP(hipMemcpyAsync(h.data(), s0, sizeof(pb_fft_sel) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
@@ -498,7 +533,9 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
             rf.poly_valid = true; rf.spec = ctx->poly_want; rf.poly = flags_of(h); rf.sel = h;
         }
     }
-    const bool have = known_flags(ctx, steps[0].info, B) != nullptr;
+    const bool have = known_flags(ctx, info, B) != nullptr;
+    // (records the estimation has just built bring their spectra with them: blur_params_kernel ends with them)
+    const bool held = ctx->spectra.holds(info, B), by_estimate = held && ctx->spectra.by_estimate();
     // (per-launch profiling keeps everything on one stream: events on the side stream would time its launches' wait
     // behind the other kernel's workgroups, not their work)
     // One-pass polynomial: the images whose spectrum is the polynomial's take ONE window pass from the first step's input
@@ -509,8 +546,7 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
     // PolySpec.always == 2 (records of the estimation): every image on three window steps, three launches of the wave body
     if (fft && !ctx->poly_want.on && ctx->poly_want.always == 2 && !have) {
         float *k = nullptr; pb_fft_sel *sel = nullptr;
-        const bool built = ctx->khat_by_estimate && ctx->khat_owner == steps[0].info && ctx->khat_B == B;
-        int rc = pb_build_khat(ctx, steps[0].info, B, &k, &sel, !built);
+        int rc = pb_build_khat(ctx, info, B, &k, &sel, !by_estimate);
         for (int s = 0; s < 3 && !rc; ++s) {
             ConvPass p = steps[s];
             p.khat = k; p.fsel = sel; p.poly = 0;
@@ -521,17 +557,15 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
     }
     const bool poly_on = fft && ctx->poly_want.on;
     const bool fold = poly_on && steps[0].out_dtype == steps[2].out_dtype;
+    const ConvPass whole = composite_pass(steps);
     auto first_step = [&](ConvPass &p) {
         if (!fold) return;
         p.poly = 2;
-        p.out2 = steps[2].out; p.out2_kind = steps[2].out_kind; p.out2_pitch = steps[2].out_pitch; p.out2_plane = steps[2].out_plane;
-        p.clamp2 = steps[2].clamp01;
+        p.out2 = whole.out; p.out2_kind = whole.out_kind; p.out2_pitch = whole.out_pitch; p.out2_plane = whole.out_plane;
+        p.clamp2 = whole.clamp01;
     };
     auto composite = [&](float *k, pb_fft_sel *sel) -> int {
-        ConvPass pc = steps[0];
-        pc.out = steps[2].out; pc.out_kind = steps[2].out_kind; pc.out_dtype = steps[2].out_dtype;
-        pc.out_pitch = steps[2].out_pitch; pc.out_plane = steps[2].out_plane;
-        pc.scale = 1.f; pc.coef = 0.f; pc.clamp01 = steps[2].clamp01; pc.poly = 1;
+        ConvPass pc = whole;
         pc.khat = k; pc.fsel = sel;
         if (!fft_pass_ok(pc)) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "one-pass polynomial: composite pass not feasible");
         return launch_tile_spectrum(ctx, pc);
@@ -539,13 +573,10 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
     // the images whose one pass runs on 128 x 128 windows (pb_fft_sel.poly == 2): a launch of their own, beside the others
     auto composite128 = [&](float *k, pb_fft_sel *sel) -> int {
         if (ctx->poly_want.on != 3) return PB_OK;
-        ConvPass pc = steps[0];
-        pc.out = steps[2].out; pc.out_kind = steps[2].out_kind; pc.out_dtype = steps[2].out_dtype;
-        pc.out_pitch = steps[2].out_pitch; pc.out_plane = steps[2].out_plane;
-        pc.scale = 1.f; pc.coef = 0.f; pc.clamp01 = steps[2].clamp01; pc.poly = 1;
+        ConvPass pc = whole;
         pc.khat = k; pc.fsel = sel;
         const std::vector<pb_fft_sel> *ksel = nullptr;
-        (void)known_flags(ctx, steps[0].info, B, &ksel);
+        (void)known_flags(ctx, info, B, &ksel);
         ctx->known_sel = ksel;
         const int rc = pb_launch_conv_w128(ctx, pc);
         ctx->known_sel = nullptr;
@@ -559,9 +590,18 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
     // or on 128 x 128 windows -- two launches on the caller's stream, each skipping the other's images, and nothing else.
     if (poly_on && ctx->poly_want.always && !have) {
         float *k = nullptr; pb_fft_sel *sel = nullptr;
-        const bool built = ctx->khat_by_estimate && ctx->khat_owner == steps[0].info && ctx->khat_B == B;
-        int rc = pb_build_khat(ctx, steps[0].info, B, &k, &sel, !built);
+        int rc = pb_build_khat(ctx, info, B, &k, &sel, !by_estimate);
         if (rc) return rc;
+        auto window_pass = [&]() -> int {
+            const int e = composite128(k, sel);
+            if (e) return e;
+            if (pb_conv_wfft_types(whole)) return composite(k, sel);
+            ConvPass p = steps[0];                           // (the composite's types are not built: the first step's launch takes them along)
+            p.khat = k; p.fsel = sel;
+            first_step(p);
+            return launch_tile_spectrum(ctx, p);
+        };
+        if (steps[0].boundary != PB_ZERO) return window_pass();
         // The zero boundary: the window pass is the polynomial of the zero-EXTENDED image, which is the three-step result
         // (every step truncated to the padded domain, filters.py:40-49) everywhere but within 24 samples of the padded border
         // -- 12 of the image's.  That frame is recomputed by three Horner steps over the ring of window pairs it depends on
@@ -569,9 +609,8 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
         // frame's tiles of the output.  A ring step is a race of single window pairs (one or two rounds of ~20 us whatever
         // its size), so the first two -- which touch neither the output nor the first set of spectra -- run on the side
         // stream BESIDE the window pass; only the third waits for both.
-        const bool zero = steps[0].boundary == PB_ZERO;
-        const bool ring_aside = zero && ctx->aux && !ctx->prof_on && ctx->zero_ring_aside;
-        auto ring_steps = [&](int s0, int s1, float *k2, pb_fft_sel *sel2) -> int {
+        float *k2 = nullptr; pb_fft_sel *sel2 = nullptr;
+        auto ring_steps = [&](int s0, int s1) -> int {
             int e = PB_OK;
             for (int s = s0; s < s1 && !e; ++s) {
                 ConvPass p = steps[s];
@@ -581,47 +620,30 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
             }
             return e;
         };
-        float *k2 = nullptr; pb_fft_sel *sel2 = nullptr;
-        int rc_side = PB_OK;
-        if (ring_aside) {
-            PB_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-            PB_HIP(hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-            hipStream_t main_stream = ctx->stream;
-            ctx->stream = ctx->aux;
-            rc_side = pb_build_khat_ring(ctx, steps[0].info, B, &k2, &sel2);
-            if (!rc_side) rc_side = ring_steps(0, 2, k2, sel2);
-            ctx->stream = main_stream;
-            PB_HIP(hipEventRecord(ctx->ev_join, ctx->aux));
+        auto first_two = [&]() -> int {
+            const int e = pb_build_khat_ring(ctx, info, B, &k2, &sel2);
+            return e ? e : ring_steps(0, 2);
+        };
+        if (ctx->aux && !ctx->prof_on) {
+            SideStream side(ctx);
+            PB_HIP(side.forked);
+            const int rc_side = side.run(first_two);
+            rc = window_pass();
+            PB_HIP(side.join());
+            if (!rc) rc = rc_side;
+        } else {
+            rc = window_pass();
+            if (!rc) rc = first_two();
         }
-        rc = composite128(k, sel);
-        ConvPass pc = steps[0];
-        pc.out_dtype = steps[2].out_dtype;
-        if (!rc) {
-            if (pb_conv_wfft_types(pc)) rc = composite(k, sel);
-            else {
-                ConvPass p = steps[0];                           // (the composite's types are not built: the first step's launch takes them along)
-                p.khat = k; p.fsel = sel;
-                first_step(p);
-                rc = launch_tile_spectrum(ctx, p);
-            }
-        }
-        if (ring_aside) PB_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));     // (joined on every way out)
-        if (rc || rc_side || !zero) return rc ? rc : rc_side;
-        if (!ring_aside) {
-            rc = pb_build_khat_ring(ctx, steps[0].info, B, &k2, &sel2);
-            if (!rc) rc = ring_steps(0, 2, k2, sel2);
-            if (rc) return rc;
-        }
-        return ring_steps(2, 3, k2, sel2);
+        return rc ? rc : ring_steps(2, 3);
     }
-    const long side_min_tiles = ctx->side_min_tiles;
+    constexpr long min_side_tiles = 12288;      // (a 4K image has 6405 stencil tiles, 32 x 1080p 53568)
     const long stencil_tiles = (long)((steps[0].H + 2 * steps[0].pad + 63) / 64) * ((steps[0].W + 2 * steps[0].pad + 63) / 64) * steps[0].P;
-    const bool side = ctx->aux && stencil_tiles >= side_min_tiles;
-    if (!fft || have || !side || ctx->prof_on) {
+    const bool side_pays = ctx->aux && stencil_tiles >= min_side_tiles;
+    if (!fft || have || !side_pays || ctx->prof_on) {
         if (fft && ctx->poly_want.on == 3) {
             float *k = nullptr; pb_fft_sel *sel = nullptr;
-            const bool built = (have || ctx->khat_by_estimate) && ctx->khat_owner == steps[0].info && ctx->khat_B == B;
-            int rc = pb_build_khat(ctx, steps[0].info, B, &k, &sel, !built);
+            int rc = pb_build_khat(ctx, info, B, &k, &sel, !(held && (have || by_estimate)));
             if (rc) return rc;
             rc = composite128(k, sel);
             if (rc) return rc;
@@ -638,49 +660,44 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
             // (the spectra the three steps have just used -- the first set's, or the second's behind an edgetaper -- and the spec they
             // were built under: images with a one-pass record wait for this launch)
             float *k = nullptr; pb_fft_sel *sel = nullptr;
-            const int rc = pb_build_khat(ctx, steps[0].info, B, &k, &sel, false);
+            const int rc = pb_build_khat(ctx, info, B, &k, &sel, false);
             if (rc) return rc;
             if (pb_spec_of_spectra(ctx, k).on) return composite(k, sel);
         }
         return PB_OK;
     }
     float *k = nullptr; pb_fft_sel *sel = nullptr;
-    // (records the estimation has just built bring their spectra with them: blur_params_kernel ends with them)
-    int rc = pb_build_khat(ctx, steps[0].info, B, &k, &sel, !(ctx->khat_by_estimate && ctx->khat_owner == steps[0].info && ctx->khat_B == B));
+    int rc = pb_build_khat(ctx, info, B, &k, &sel, !by_estimate);
     if (rc) return rc;
-    PB_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-    PB_HIP(hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-    hipStream_t main_stream = ctx->stream;
     // Which launches stay on the caller's stream: those that probably do the work -- crossing to the side stream and back
-    // costs two queue-to-queue waits (~5 us each) on the critical path.  Where the spec admits 128 x 128 windows (images of
-    // poly_min_pairs128 window pairs or more: decided from the sizes alone, api.hip) that is the 128 x 128 launch, and the
-    // wave body's three launches join the stencil launches on the side stream; otherwise the wave body's.
-    const int main_env = ctx->main_stream_body;     // 0 = wave body, 1 = 128 x 128
-    const bool w128_main = poly_on && ctx->poly_want.on == 3 && ctx->poly_want.cost128 > 0.f && main_env != 0;
-    auto wave_steps = [&]() {
-        for (int s = 0; s < 3 && !rc; ++s) {
+    // costs two queue-to-queue waits (~5 us each) on the critical path.  Where the spec admits 128 x 128 windows that is the
+    // 128 x 128 launch, and the wave body's three launches join the stencil launches on the side stream; otherwise the wave body's.
+    const bool w128_main = poly_on && ctx->poly_want.on == 3;
+    auto wave_steps = [&]() -> int {
+        int e = PB_OK;
+        for (int s = 0; s < 3 && !e; ++s) {
             ConvPass p = steps[s];
             p.khat = k; p.fsel = sel;
             if (s == 0) first_step(p);
-            rc = launch_tile_spectrum(ctx, p);
+            e = launch_tile_spectrum(ctx, p);
         }
+        return e;
     };
-    ctx->stream = ctx->aux;
-    // (the composite pass touches other images than the steps' launches do: it, too, runs -- or finds no work -- beside them)
-    if (poly_on && !w128_main) rc = composite128(k, sel);
-    if (poly_on && !fold && !rc) rc = composite(k, sel);
-    if (w128_main) wave_steps();
-    for (int s = 0; s < 3 && !rc; ++s) {
-        ConvPass p = steps[s];
-        p.khat = k; p.fsel = sel;
-        rc = launch_stencil(ctx, p);
-    }
-    ctx->stream = main_stream;
-    // (whatever was queued on the side stream is joined on every path out of here: later calls share the scratch planes)
-    PB_HIP(hipEventRecord(ctx->ev_join, ctx->aux));
-    if (w128_main) { if (!rc) rc = composite128(k, sel); }
-    else wave_steps();
-    PB_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+    SideStream side(ctx);
+    PB_HIP(side.forked);
+    rc = side.run([&]() -> int {
+        // (the composite pass touches other images than the steps' launches do: it, too, runs -- or finds no work -- beside them)
+        int e = poly_on && !fold ? composite(k, sel) : PB_OK;
+        if (w128_main && !e) e = wave_steps();
+        for (int s = 0; s < 3 && !e; ++s) {
+            ConvPass p = steps[s];
+            p.khat = k; p.fsel = sel;
+            e = launch_stencil(ctx, p);
+        }
+        return e;
+    });
+    if (!rc) rc = w128_main ? composite128(k, sel) : wave_steps();
+    PB_HIP(side.join());
     return rc;
 }
 
@@ -700,40 +717,26 @@ int pb_cache_records(pb_ctx *ctx, const pb_blur_info *info, int B) {
     ctx->rec_cache[info] = f;
     return PB_OK;
 }
-// a write of `bytes` bytes at dst: forget what is known about the record sets it overlaps
+// a write of `bytes` bytes at dst: forget what is known about the record sets it overlaps -- what the host read back about
+// them, whether their taps are point-symmetric, and either set of spectra built from them
 void pb_forget_range(pb_ctx *ctx, const void *dst, size_t bytes) {
     const char *lo = static_cast<const char *>(dst), *hi = lo + bytes;
-    for (auto it = ctx->rec_cache.begin(); it != ctx->rec_cache.end();) {
-        const char *a = static_cast<const char *>(it->first), *b = a + sizeof(pb_blur_info) * (size_t)it->second.B;
-        if (a < hi && lo < b) {
-            if (ctx->khat_owner == it->first) { ctx->khat_owner = nullptr; ctx->khat_B = 0; ctx->khat_by_estimate = false; }
-            it = ctx->rec_cache.erase(it);
-        } else ++it;
-    }
-    for (auto it = ctx->flip_sets.begin(); it != ctx->flip_sets.end();) {
-        const char *a = static_cast<const char *>(it->first), *b = a + sizeof(pb_blur_info) * (size_t)it->second.B;
-        if (a < hi && lo < b) it = ctx->flip_sets.erase(it); else ++it;
-    }
+    auto erase_overlapping = [&](auto &sets) {
+        for (auto it = sets.begin(); it != sets.end();) {
+            const char *a = static_cast<const char *>(it->first), *b = a + sizeof(pb_blur_info) * (size_t)it->second.B;
+            if (a < hi && lo < b) it = sets.erase(it); else ++it;
+        }
+    };
+    erase_overlapping(ctx->rec_cache);
+    erase_overlapping(ctx->flip_sets);
+    ctx->spectra.drop_if_overlaps(lo, hi);
+    ctx->spectra2.drop_if_overlaps(lo, hi);
 }
-void pb_forget_records(pb_ctx *ctx, const void *info, int B) {
-    if (info) {
-        pb_forget_range(ctx, info, sizeof(pb_blur_info) * (size_t)B);
-        // (device-built records are not in the cache, but the spectra scratch may be theirs)
-        const char *a = static_cast<const char *>(info), *b = a + sizeof(pb_blur_info) * (size_t)B, *o = static_cast<const char *>(ctx->khat_owner);
-        // (spectra of a run of records that overlaps the rewritten ones anywhere, not only at its first record)
-        const char *oe = o ? o + sizeof(pb_blur_info) * (size_t)ctx->khat_B : nullptr;
-        if (o && o < b && a < oe) { ctx->khat_owner = nullptr; ctx->khat_B = 0; ctx->khat_by_estimate = false; }
-        const char *o2 = static_cast<const char *>(ctx->khat2_owner);
-        const char *oe2 = o2 ? o2 + sizeof(pb_blur_info) * (size_t)ctx->khat2_B : nullptr;
-        if (o2 && o2 < b && a < oe2) { ctx->khat2_owner = nullptr; ctx->khat2_B = 0; }
-        return;
-    }
+// everything the context merely remembers to save launches (flip_sets are facts about caller data: pb_forget_range only)
+void pb_forget_hints(pb_ctx *ctx) {
     ctx->rec_cache.clear();
-    ctx->flip_sets.clear();
-    ctx->khat2_owner = nullptr; ctx->khat2_B = 0;
-    ctx->khat_owner = nullptr;
-    ctx->khat_B = 0;
-    ctx->khat_by_estimate = false;
+    ctx->spectra.drop();
+    ctx->spectra2.drop();
 }
 
 static int launch_stencil(pb_ctx *ctx, const ConvPass &p) {

@@ -341,7 +341,7 @@ int pb_khat_buffers(pb_ctx *ctx, int B, float **khat, pb_fft_sel **sel) {
     if (!k || !s) return PB_ERR_NOMEM;
     s += (size_t)(ctx->sel_slot % PB_SEL_SLOTS) * B;
     ctx->sel_B = B; ctx->sel_last = ctx->sel_slot;
-    if (k != ctx->khat_buf) { ctx->khat_buf = k; ctx->khat_owner = nullptr; ctx->khat_B = 0; ctx->khat_by_estimate = false; }   // (the scratch buffer was reallocated)
+    ctx->spectra.rebind(k);
     *khat = k; *sel = s;
     return PB_OK;
 }
@@ -351,14 +351,9 @@ int pb_khat2_buffers(pb_ctx *ctx, int B, float **khat, pb_fft_sel **sel) {
     pb_fft_sel *s = static_cast<pb_fft_sel *>(pb_scratch(ctx, "conv.fftsel2", sizeof(pb_fft_sel) * (size_t)B * PB_SEL_SLOTS));
     if (!k || !s) return PB_ERR_NOMEM;
     s += (size_t)(ctx->sel_slot % PB_SEL_SLOTS) * B;          // (one slot per iteration, as pb_khat_buffers)
-    if (k != ctx->khat2_buf) { ctx->khat2_buf = k; ctx->khat2_owner = nullptr; ctx->khat2_B = 0; }      // (the scratch buffer was reallocated)
+    ctx->spectra2.rebind(k);
     *khat = k; *sel = s;
     return PB_OK;
-}
-// whether the second set holds the spectra of these records under this spec (the estimation built them: estimate.hip)
-static bool khat2_holds(pb_ctx *ctx, const pb_blur_info *info, int B, const PolySpec &spec) {
-    return ctx->khat2_owner && ctx->khat2_owner == info && ctx->khat2_B == B && same_spec(ctx->khat2_spec, spec) &&
-           (spec.on != 0 || ctx->khat2_spec.always == spec.always);
 }
 int pb_build_khat(pb_ctx *ctx, const pb_blur_info *info, int B, float **khat, pb_fft_sel **sel, bool launch) {
     float *k = nullptr; pb_fft_sel *s = nullptr;
@@ -367,22 +362,21 @@ int pb_build_khat(pb_ctx *ctx, const pb_blur_info *info, int B, float **khat, pb
     // (spectra of other records, of fewer records than this pass covers, or of the kernel where the pass wants the polynomial's)
     // (... or selections written to another slot than the one this pass reads)
     // (the estimation may have built what this pass wants into the SECOND set: the polynomial behind an edgetaper)
-    if ((!ctx->khat_owner || ctx->khat_owner != info || ctx->khat_B != B || !same_spec(ctx->poly_built, ctx->poly_want)) &&
-        ctx->poly_want.on != 0 && khat2_holds(ctx, info, B, ctx->poly_want)) {
+    const int slot = ctx->sel_slot % PB_SEL_SLOTS;
+    const bool held = ctx->spectra.holds(info, B, ctx->poly_want);
+    if (!held && ctx->poly_want.on != 0 && ctx->spectra2.holds(info, B, ctx->poly_want)) {
         float *k2 = nullptr; pb_fft_sel *s2 = nullptr;
         const int rc2 = pb_khat2_buffers(ctx, B, &k2, &s2);
         if (rc2) return rc2;
-        if (khat2_holds(ctx, info, B, ctx->poly_want)) {
-            ctx->sel2_mask |= 1u << (ctx->sel_slot % PB_SEL_SLOTS);
+        if (ctx->spectra2.holds(info, B, ctx->poly_want)) {      // (still: the scratch may have moved)
+            ctx->sel2_mask |= 1u << slot;
             *khat = k2; *sel = s2;
             return PB_OK;
         }
     }
-    if (!ctx->khat_owner || ctx->khat_owner != info || ctx->khat_B != B || !same_spec(ctx->poly_built, ctx->poly_want) ||
-        ctx->khat_slot != ctx->sel_slot % PB_SEL_SLOTS) launch = true;
+    if (!held || ctx->spectra.slot() != slot) launch = true;
     if (launch) {
-        ctx->khat_owner = info; ctx->khat_B = B; ctx->khat_by_estimate = false; ctx->poly_built = ctx->poly_want;
-        ctx->khat_slot = ctx->sel_slot % PB_SEL_SLOTS;
+        ctx->spectra.claim(info, B, ctx->poly_want, slot, false);
         ProfScope prof(ctx, PB_PROF_PARAMS);
         hipLaunchKernelGGL(khat_kernel, dim3((unsigned)B, KH_SLICES), dim3(KH_NT), 0, ctx->stream, info, k, s, ctx->fft_min_phases,
                            ctx->poly_want);
@@ -401,11 +395,11 @@ int pb_build_khat_ring(pb_ctx *ctx, const pb_blur_info *info, int B, float **kha
     if (rcb) return rcb;
     PolySpec ps = no_poly();
     ps.always = 2;
-    if (!khat2_holds(ctx, info, B, ps)) {
+    if (!ctx->spectra2.holds(info, B, ps)) {
         ProfScope prof(ctx, PB_PROF_PARAMS);
         hipLaunchKernelGGL(khat_kernel, dim3((unsigned)B, KH_SLICES), dim3(KH_NT), 0, ctx->stream, info, k, s, ctx->fft_min_phases, ps);
         PB_LAUNCH_CHECK();
-        ctx->khat2_owner = info; ctx->khat2_B = B; ctx->khat2_spec = ps;
+        ctx->spectra2.claim(info, B, ps, ctx->sel_slot % PB_SEL_SLOTS, false);
     }
     *khat = k; *sel = s;
     return PB_OK;

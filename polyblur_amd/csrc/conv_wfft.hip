@@ -785,12 +785,11 @@ __global__ __launch_bounds__(64, 2) void conv_wfft_kernel(const ConvPass a, cons
 
 // The output extent of a pass and the largest job list its records may ask for: `poly2` = the records may carry one-pass
 // images with the composite filter's halos (PolySpec.on == 2: tiles down to PB_POLY_MIN_TX x PB_POLY_MIN_TY, but never
-// smaller in area than the cost model of khat.h admits); otherwise halos are at most 12.  pairs12 = window pairs per plane at
-// the 12-sample halo.  (Counts stay below 2^20: the kernel divides with reciprocals.)
-bool wfft_geometry(const ConvPass &p, bool poly2, float min_area, WGeom &g, long &per_max, long &pairs12) {
+// smaller in area than the cost model of khat.h admits); otherwise halos are at most 12.  (Counts stay below 2^20: the kernel divides with reciprocals.)
+bool wfft_geometry(const ConvPass &p, bool poly2, float min_area, WGeom &g, long &per_max) {
     g.oh = (p.out_kind == OUT_INTERIOR) ? p.H : p.H + 2 * p.pad;
     g.ow = (p.out_kind == OUT_INTERIOR) ? p.W : p.W + 2 * p.pad;
-    per_max = 0; pairs12 = 0;
+    per_max = 0;
     for (int hx = 4; hx <= 28; hx += 4) {
         for (int hy = 2; hy <= 30; hy += 2) {
             const int tx = FT_N - 2 * hx, ty = FT_N - 2 * hy;
@@ -800,7 +799,6 @@ bool wfft_geometry(const ConvPass &p, bool poly2, float min_area, WGeom &g, long
             const long nj = (long)(((g.ow + tx - 1) / tx + 1) / 2) * ((g.oh + ty - 1) / ty);
             if (nj > (1L << 20)) return false;
             per_max = std::max(per_max, (nj + 7) / 8);
-            if (hx == 12 && hy == 12) pairs12 = nj;
         }
     }
     const long total = 8 * per_max * p.P;
@@ -831,10 +829,10 @@ extern "C" int pb_debug_wf_trace(unsigned long long *host, int n_waves) {
 }
 #endif
 
-// (as pb_conv_w128_feasible: the largest job list a pass with one-pass images of `min_area`-sample tiles may need)
-bool pb_conv_wfft_feasible(const ConvPass &p, bool poly2, int min_area) {
-    WGeom g; long per_max = 0, pairs12 = 0;
-    return wfft_geometry(p, poly2, (float)min_area, g, per_max, pairs12);
+// (as pb_conv_w128_feasible: the largest job list a pass with one-pass images of the smallest tiles may need)
+bool pb_conv_wfft_feasible(const ConvPass &p, bool poly2) {
+    WGeom g; long per_max = 0;
+    return wfft_geometry(p, poly2, (float)PB_POLY_MIN_AREA, g, per_max);
 }
 
 bool pb_conv_wfft_types(const ConvPass &p) {
@@ -850,25 +848,21 @@ bool pb_conv_wfft_types(const ConvPass &p) {
 // whatever the size of the launch, a 512-thread workgroup ~8 us, so a three-step pass of a few hundred pairs is a race of
 // single pairs that the workgroup form used to win (700 x 500: 0.31 against 0.38 ms per call); with small images' polynomials
 // mostly one window pass now, the call is faster through this form alone (0.29 ms; 1080p 0.45 against 0.53).
-// PB_WAVE_MIN_JOBS=n in the environment sends passes of fewer than n pairs to the workgroup form again.
 int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p) {
-    const long min_jobs = ctx->wave_min_jobs;
     if (!pb_conv_wfft_types(p)) return PB_ERR_UNSUPPORTED;
     const bool poly2 = p.poly != 0 && pb_spec_of_spectra(ctx, p.khat).on >= 2;
-    const float min_area = (float)ctx->poly_min_area;      // (the smallest one-pass tile the cost model of khat.h admits)
+    const float min_area = (float)PB_POLY_MIN_AREA;        // (the smallest one-pass tile the cost model of khat.h admits)
     WGeom g;
-    long per_max = 0, pairs12 = 0;
-    if (!wfft_geometry(p, poly2, min_area, g, per_max, pairs12)) {
+    long per_max = 0;
+    if (!wfft_geometry(p, poly2, min_area, g, per_max)) {
         if (poly2) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "conv pass: too many windows for the tile-spectrum body");
         return PB_ERR_UNSUPPORTED;
     }
-    long jobs = pairs12 * p.P;
     long groups = 8L * per_max * p.P;                       // list entries if every image had the smallest tiles its records may select
     if (ctx->known_sel) {
         // the host has the records' choices (it built them): the grid is exactly the list of this launch's jobs
         const int B = p.P / p.C;
-        long per_sum = 0;
-        jobs = 0;
+        long per_sum = 0, jobs = 0;
         for (int b = 0; b < B && b < (int)ctx->known_sel->size(); ++b) {
             const pb_fft_sel &e = (*ctx->known_sel)[(size_t)b];
             const bool takes = e.use_fft && e.poly != 2 && (p.poly == 2 || (e.poly != 0) == (p.poly != 0));      // (poly_match, conv_fft_common.h)
@@ -880,7 +874,6 @@ int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p) {
         if (!jobs) return PB_OK;                            // nothing in this launch for any image
         groups = 8L * per_sum * p.C;                        // (the kernel's list: the images' shares of every plane, back to back)
     }
-    if (!poly2 && jobs < min_jobs) return PB_ERR_UNSUPPORTED;
     ProfScope prof(ctx, PB_PROF_CONV_FFT);
     // fp32 planes; the second and third Horner step of fp16 images (fp32 temporaries in, fp16 x operand, fp32 or fp16 out);
     // the first step and the one-pass polynomial of fp16 images (fp16 window)

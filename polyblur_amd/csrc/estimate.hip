@@ -1537,19 +1537,17 @@ template <typename K> int allow_lds(pb_ctx *ctx, K kernel, size_t bytes) {
 // (measured, 4K: 73.7 -> 68.5 us; 8 x 1080p: 132 -> 122 us; 512 threads on the narrow tile: 95 us; one 700x500 image,
 // whose 44 narrow tiles already leave most CUs idle: 31.7 -> 35.9 us, hence the workgroup-count condition).
 int pick_lognb(pb_ctx *ctx, const FftPlan *pl, int W, int P, bool wide_ok, int *threads, bool fixed_maxima = false) {
-    const int forced = ctx->fft_lognb;
     if (fft_lds_bytes(pl, 1) > kMaxLds) {          // lines through global memory (grad_cols_long_kernel): 8-column tiles
         int lognb = 2;
         while (lognb > 0 && (2 << (lognb - 1)) >= W * 2) --lognb;
         if (threads) *threads = LONG_NT;
         return lognb;
     }
-    int lognb = forced >= 0 ? forced : 3;
+    int lognb = 3;
     while (lognb > 0 && fft_lds_bytes(pl, 1 << lognb) > 80 * 1024) --lognb;
     while (lognb > 0 && (2 << (lognb - 1)) >= W * 2) --lognb;
     int nt = NT;
-    const bool wide_off = ctx->cols_wide == 0;
-    if (wide_ok && !wide_off && forced < 0 && !pl->bluestein_m && pl->nstage >= 2 &&
+    if (wide_ok && !pl->bluestein_m && pl->nstage >= 2 &&
         fft_lds_bytes(pl, 2 << lognb) <= 140 * 1024 && (long)P * (W / (4 << lognb)) >= 200 &&   // still fills the chip
         // (1080-point lines through lines_fixed.hip: two 512-thread workgroups per CU on 16-column tiles -- 69 KB each, one's
         // requests under the other's stages -- beat one 1024-thread workgroup on a 32-column tile: 32 x 1080p 174 against 198 us)
@@ -1572,50 +1570,11 @@ long long_grid(long items, size_t slot_bytes) {
 // flight.  Lines of up to 4096 samples (32 KB of LDS per two rows) fit five workgroups per CU; with many more
 // workgroups than that they run 128 threads.  Longer lines are limited by LDS to two or three workgroups per CU and
 // keep 256 threads (measured at 7680: 241 us per 8K image against 339 us with 128).
-#ifdef PB_EXPERIMENTAL
-// The directional maxima of (gx, gy) planes (blur_estimation.py:122-134, under the saturation mask :117-118) as a pass of
-// its own: what grad_cols_kernel<1> folds in its epilogue, for the estimation of a single small batch whose row and column
-// transforms run side by side on two streams (pb_estimate_impl).  One partial per workgroup in the layout of the column
-// tiles' partials (blur_params_kernel folds them); the same products and the same maximum: bit-identical results.
-template <int NA>
-__global__ __launch_bounds__(NT) void dir_maxima_kernel(const float *__restrict__ gx, const float *__restrict__ gy,
-                                                         const float *__restrict__ gray, long HW, int bpp, unsigned *__restrict__ mags,
-                                                         int tiles_pad, int n_angles, int discard_sat, float thr, AngleTable ang) {
-    __shared__ float red[(NT / 64) * PB_MAX_ANGLES];
-    const int plane = blockIdx.x / bpp, blk = blockIdx.x - plane * bpp;
-    const float *px = gx + (long)plane * HW, *py = gy + (long)plane * HW, *pg = gray + (long)plane * HW;
-    float best[PB_MAX_ANGLES];
-#pragma unroll
-    for (int k = 0; k < PB_MAX_ANGLES; ++k) best[k] = 0.f;
-    const int na = n_angles + 1;
-    auto fold = [&](float dx, float dy, float g) {
-        if (discard_sat && g > thr) return;
-#pragma unroll
-        for (int k = 0; k < (NA ? NA : PB_MAX_ANGLES); ++k)
-            if (NA || k < na) best[k] = fmaxf(best[k], pbfft::dir_abs(ang.cs[k], ang.sn[k], dx, dy));
-    };
-    if ((HW & 3) == 0) {
-        const long n4 = HW >> 2;
-        for (long i = (long)blk * NT + threadIdx.x; i < n4; i += (long)bpp * NT) {
-            const float4 a = reinterpret_cast<const float4 *>(px)[i], b = reinterpret_cast<const float4 *>(py)[i];
-            float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (discard_sat) g = reinterpret_cast<const float4 *>(pg)[i];
-            fold(a.x, b.x, g.x); fold(a.y, b.y, g.y); fold(a.z, b.z, g.z); fold(a.w, b.w, g.w);
-        }
-    } else {
-        for (long i = (long)blk * NT + threadIdx.x; i < HW; i += (long)bpp * NT) fold(px[i], py[i], discard_sat ? pg[i] : 0.f);
-    }
-    reduce_maxima<NT>(best, red, mags + (long)plane * PB_MAX_ANGLES * tiles_pad + blk, tiles_pad, n_angles);
-}
-
-#endif
-
 // How many threads the row kernels run a line pair with (launch_rows and launch_gray_rows; the comments there).
 static int rows_threads(pb_ctx *ctx, const FftPlan *pl, size_t lds, long blocks) {
-    const int force_nt = ctx->rows_nt;
     const bool one_round = blocks <= 256L * 5;
-    if (!plan_ext(pl) && lds <= 32 * 1024 && (force_nt == 128 || (force_nt != 256 && !one_round))) return 128;
-    if (plan_ext(pl) || force_nt == 512 || (force_nt == 0 && lds > 40 * 1024)) return 512;
+    if (!plan_ext(pl) && lds <= 32 * 1024 && !one_round) return 128;
+    if (plan_ext(pl) || lds > 40 * 1024) return 512;
     return 256;
 }
 
@@ -1896,7 +1855,7 @@ int pb_fourier_gradients_typed(pb_ctx *ctx, const float *planes, int P, int H, i
 }
 
 bool pb_gradient_planes_half(pb_ctx *ctx, int H, int W) {
-    return ctx->cols_fixed && ctx->rows_fixed && ctx->fft_lognb < 0 && ctx->fft_first < 0 && ctx->fft_first_rows < 0 &&
+    return ctx->cols_fixed && ctx->rows_fixed && ctx->fft_first < 0 && ctx->fft_first_rows < 0 &&
            ctx->fft_ext_radix != 0 && pb_lines_fixed_shape(H, W);
 }
 
@@ -1913,17 +1872,7 @@ int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H
     if (!plh) return PB_ERR_NOMEM;
     const int est_lognb = pick_lognb(ctx, plh, W, B, opt->n_angles == 6, nullptr, opt->n_angles == 6 && !(opt->q > 0.f) && ctx->cols_fixed);   // as launch_cols
     const int col_tiles = (W + (2 << est_lognb) - 1) / (2 << est_lognb);
-    // (see below: transforms side by side + a maxima pass; an experiment that measured SLOWER -- 0.90 against 0.85 ms per 4K call,
-    // 0.35 against 0.32 ms at 700 x 500: the column workgroups take a CU's whole LDS, so the row workgroups do not run beside
-    // them, and the maxima pass and the fork / join come on top -- and is only in the --experimental build, behind PB_EST_OVERLAP=1)
-#ifdef PB_EXPERIMENTAL      // (python -m polyblur_amd.build --experimental)
-    const int overlap_env = ctx->est_overlap;
-    const bool lines_in_lds = pb_fft_length_supported(H) == 1 && pb_fft_length_supported(W) == 1;
-    const bool overlap = ctx->aux && !ctx->prof_on && lines_in_lds && overlap_env > 0;
-#else
-    const bool overlap = false;
-#endif
-    const int est_tiles = overlap ? 512 : col_tiles;          // partial maxima per image: column tiles, or the maxima pass's workgroups
+    const int est_tiles = col_tiles;                          // partial maxima per image: one per column tile
     float *gray = static_cast<float *>(pb_scratch(ctx, "est.gray", sizeof(float) * B * HW));
     float *gx = static_cast<float *>(pb_scratch(ctx, "est.gx", sizeof(float) * B * HW));
     unsigned *mm = static_cast<unsigned *>(pb_scratch(ctx, "est.mm", sizeof(unsigned) * 2 * B));
@@ -1935,7 +1884,7 @@ int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H
     int bpi_q0 = 0;
     // q == 0: gray, its range and the row transform in one launch where the lines allow it
     bool rows_done = false;
-    if (opt->q <= 0.f && !overlap) {
+    if (opt->q <= 0.f) {
         float2 *pt = nullptr;
         const int rcg = launch_gray_rows(ctx, in, dtype, B, C, H, W, gray, gx, &pt, &bpi_q0);
         if (rcg == PB_OK) { rows_done = true; part_q0 = pt; }
@@ -1989,45 +1938,10 @@ int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H
     }
     const bool norm = opt->q > 0.f;                  // q == 0: transforms of the un-normalised image, maxima rescaled afterwards
     int rc = PB_OK;
-#ifdef PB_EXPERIMENTAL
-    if (overlap) {
-        // (experiment, PB_EST_OVERLAP=1) both transforms are chains of dependent stages on an under-filled chip, so they are
-        // issued side by side -- rows (-> gx) on the side stream, a gy-writing column pass here -- and one HBM-speed pass
-        // folds the maxima.  Same results bit for bit; measured slower (above).
-        float *gy = static_cast<float *>(pb_scratch(ctx, "est.gy", sizeof(float) * B * HW));
-        if (!gy) return PB_ERR_NOMEM;
-        PB_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-        PB_HIP(hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->aux;
-        rc = launch_rows(ctx, gray, gx, B, H, W, norm, mm, 1);
-        ctx->stream = main_stream;
-        PB_HIP(hipEventRecord(ctx->ev_join, ctx->aux));
-        if (!rc) rc = launch_cols(ctx, gray, nullptr, gy, B, H, W, 0, norm, mm, 1, nullptr, opt->n_angles, 0);
-        PB_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        if (rc) return rc;
-        AngleTable ang;
-        for (int k = 0; k < PB_MAX_ANGLES; ++k) {
-            const float t = opt->n_angles > 0 ? 3.14159265358979323846f * (float)k / (float)opt->n_angles : 0.f;
-            ang.cs[k] = std::cos(t); ang.sn[k] = std::sin(t);
-        }
-        ProfScope prof(ctx, PB_PROF_GRAD_COLS);
-        const int tp = (est_tiles + 3) & ~3;
-        if (opt->n_angles == 6)
-            hipLaunchKernelGGL(dir_maxima_kernel<7>, dim3((unsigned)(B * est_tiles)), dim3(NT), 0, ctx->stream, gx, gy, gray, HW, est_tiles, mags, tp,
-                               opt->n_angles, opt->discard_saturation, 0.99f, ang);
-        else
-            hipLaunchKernelGGL(dir_maxima_kernel<0>, dim3((unsigned)(B * est_tiles)), dim3(NT), 0, ctx->stream, gx, gy, gray, HW, est_tiles, mags, tp,
-                               opt->n_angles, opt->discard_saturation, 0.99f, ang);
-        PB_LAUNCH_CHECK();
-    } else
-#endif
-    {
-        if (!rows_done) rc = launch_rows(ctx, gray, gx, B, H, W, norm, mm, 1);
-        if (rc) return rc;
-        rc = launch_cols(ctx, gray, gx, nullptr, B, H, W, 1, norm, mm, 1, mags, opt->n_angles, opt->discard_saturation);
-        if (rc) return rc;
-    }
+    if (!rows_done) rc = launch_rows(ctx, gray, gx, B, H, W, norm, mm, 1);
+    if (rc) return rc;
+    rc = launch_cols(ctx, gray, gx, nullptr, B, H, W, 1, norm, mm, 1, mags, opt->n_angles, opt->discard_saturation);
+    if (rc) return rc;
     float *khat = nullptr;
     pb_fft_sel *fsel = nullptr;
     if (ctx->fft_min_phases >= 0) {
@@ -2040,7 +1954,7 @@ int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H
     float *khat2 = nullptr;
     pb_fft_sel *fsel2 = nullptr;
     const PolySpec ps2 = ctx->poly_want2;
-    ctx->khat2_owner = ctx->khat2_owner == dev_info ? nullptr : ctx->khat2_owner;       // (these records are being rewritten)
+    ctx->spectra2.drop_if_overlaps(dev_info, dev_info + B);       // (these records are being rewritten)
     if (khat && (ps2.on != 0 || ps2.always != 0)) {
         rc = pb_khat2_buffers(ctx, B, &khat2, &fsel2);
         if (rc) return rc;
@@ -2053,8 +1967,8 @@ int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H
                        (!(ksize & 1) && opt->boundary == PB_WRAP) ? 1 : 0, norm ? nullptr : part_q0, bpi_q0, mm, khat, fsel,
                        ctx->fft_min_phases, ctx->poly_want, lean, khat2, fsel2, ps2, set2 ? set1 : 0);
     PB_LAUNCH_CHECK();
-    if (khat2) { ctx->khat2_owner = dev_info; ctx->khat2_B = B; ctx->khat2_spec = ps2; }
-    if (khat) { ctx->khat_owner = dev_info; ctx->khat_B = B; ctx->khat_by_estimate = true; ctx->poly_built = ctx->poly_want; ctx->khat_slot = ctx->sel_slot % PB_SEL_SLOTS; }
+    if (khat2) ctx->spectra2.claim(dev_info, B, ps2, ctx->sel_slot % PB_SEL_SLOTS, true);
+    if (khat) ctx->spectra.claim(dev_info, B, ctx->poly_want, ctx->sel_slot % PB_SEL_SLOTS, true);
     return PB_OK;
 }
 

@@ -183,6 +183,25 @@ def test_caller_kernels_that_are_not_point_symmetric(eng, method, boundary):
     assert maxabs(eng.convolve2d(xp, buf, boundary), ref.convolve2d(xp, ks[:, None], method=method)) < 2e-6
 
 
+def test_not_point_symmetric_kernels_outlive_set_dense_eval(eng):
+    """which record sets hold taps that are not point-symmetric is a fact about the caller's data, not one of the context's
+    disposable hints: pb_set_dense_eval drops the hints (which body each cached record takes has changed) and must leave that
+    fact alone -- it used to clear it, and the wrap boundary then correlated again.  The oracle's true convolution
+    (method='fft', filters.py:33-36) after each switch of the evaluation mode"""
+    ks = _odd_kernels()
+    x, _ = synthetic_blurry_batch(ks.shape[0], 3, 150, 210, seed0=42)
+    xp = ref.replicate_pad(x, capi.PB_KSIZE // 2)
+    want = ref.convolve2d(xp, ks[:, None], method="fft")
+    buf = eng.set_kernels(ks)
+    try:
+        eng.set_dense_eval("stencil")
+        assert maxabs(eng.convolve2d(xp, buf, capi.PB_WRAP), want) < 2e-6
+        eng.set_dense_eval("auto", capi.PB_DENSE_MIN_PHASES)
+        assert maxabs(eng.convolve2d(xp, buf, capi.PB_WRAP), want) < 2e-6
+    finally:
+        eng.set_dense_eval("auto", capi.PB_DENSE_MIN_PHASES)
+
+
 @pytest.mark.parametrize("name", ["stages_A.npz", "stages_B.npz", "stages_C.npz"])
 @pytest.mark.parametrize("kname", ["kest", "kwide"])
 def test_inverse_filter_fft(eng, golden, name, kname):
