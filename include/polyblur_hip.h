@@ -273,6 +273,47 @@ int pb_convolve2d(pb_ctx *ctx, const float *in, float *out, int B, int C, int Hp
 int pb_edgetaper(pb_ctx *ctx, const float *in, float *out, int B, int C, int Hp, int Wp,
                  const pb_blur_info *dev_info, int boundary);
 
+/* ---- caller-owned kernel sets: the non-blind step with a PSF of the caller's, any kh x kw with 1 <= kh <= 49 and
+ * 2 <= kw <= 49 (even, odd, square or rectangular) -- a calibrated lens blur, a motion streak, one kernel per colour plane.
+ * The reference's inverse_filtering_rank3, filters.convolve2d and edgetaper.edgetaper take such a (B,C,h,w) kernel tensor
+ * directly (deblurring.py:211-239, filters.py:14-37, edgetaper.py:26-33).
+ *
+ * pb_taps_create: host_taps holds B kernels of kh x kw floats, row-major, in the orientation of the reference's kernel
+ * tensors (correlate=True is rot90(kernel, 2) on the host, deblurring.py:225-226); the taps are used as given -- nothing is
+ * normalised.  One kernel per image; a caller with one kernel per plane passes its (B,C,H,W) batch as B*C one-channel images.
+ * With PB_ZERO the kernel is applied as F.conv2d(padding='same') applies it (filters.py:40-49): tap (i, j) multiplies the
+ * sample (i - (kh-1)/2, j - (kw-1)/2) away from the output.  With PB_WRAP as the circular convolution with the PSF rolled by
+ * -(kh/2), -(kw/2) (p2o, filters.py:255-273): tap (i, j) multiplies the sample (kh/2 - i, kw/2 - j) away.  The set keeps both
+ * forms in device memory of its own -- 25 x 25 records where the kernel fits them, tap tables of the large-kernel pass
+ * otherwise --, valid across any other call on the context until pb_taps_free, which must come before pb_destroy.
+ * Synchronises.  PB_ERR_BADARG: kw == 1 (the reference's crop [0:-0] is empty, utils.py:63-67); PB_ERR_UNSUPPORTED: a side above 49.
+ * `support`: pb_support, as for pb_set_kernels.                                                                            */
+typedef struct pb_taps pb_taps;
+int pb_taps_create(pb_ctx *ctx, int B, int kh, int kw, const float *host_taps, int support, pb_taps **taps);
+int pb_taps_free(pb_taps *taps);
+
+/* filters.convolve2d(img, kernel, method) (filters.py:14-37) on a (B,C,H,W) float32 image that is the whole domain: zero
+ * outside it (PB_ZERO) or circular over it (PB_WRAP).  out may not alias in.  PB_ERR_BADARG: kh > H - 1 or kw > W - 1.
+ * PB_ERR_UNSUPPORTED: PB_WRAP with a kernel taller than wide (kh/2 > kw/2) -- the reference pads circularly by the half-WIDTH
+ * only (filters.py:33, utils.py:48-61), so its result there is no circular convolution over the given domain; also below.   */
+int pb_convolve2d_taps(pb_ctx *ctx, const float *in, float *out, int B, int C, int H, int W, const pb_taps *taps,
+                       int boundary);
+
+/* edgetaper.edgetaper(img, kernel, n_tapers, method) (edgetaper.py:26-33) on the same kind of image: n_tapers >= 0 blends
+ * with the weights of THIS kernel -- autocorrelations of its two projections (edgetaper.py:10-23), up to 49 lags.          */
+int pb_edgetaper_taps(pb_ctx *ctx, const float *in, float *out, int B, int C, int H, int W, const pb_taps *taps,
+                      int boundary, int n_tapers);
+
+/* inverse_filtering_rank3(img, kernel, alpha, b, ..., method) (deblurring.py:211-239) for fp32 or fp16 images: replicate pad
+ * by kw / 2 on all four sides (utils.py:48-61: the kernel's height plays no part) -> [three edgetaper blends] -> polynomial
+ * -> crop -> [halo masking] -> clamp to [0, 1].  grad0_x / grad0_y: (B,C,H,W) float32 or both NULL -- the reference's
+ * grad_img=None: the gradients of the (tapered) image itself, deblurring.py:200-201.  PB_ERR_BADARG: kh > H + 2 (kw/2) - 1.
+ * A kernel taller than wide is taken by the plain polynomial under either boundary (compute_polynomial_fft is circular over
+ * the padded domain, deblurring.py:141-169) and refused with PB_WRAP and edgetaping (PB_ERR_UNSUPPORTED, as above).        */
+int pb_inverse_filter_taps(pb_ctx *ctx, const void *in, void *out, int dtype, int B, int C, int H, int W,
+                           const pb_taps *taps, float alpha, float beta, int boundary, int edgetaping,
+                           int remove_halo, const float *grad0_x, const float *grad0_y);
+
 /* halo_masking (deblurring.py:193-208), bug-compatible.  All (B,C,H,W) float32.           */
 int pb_halo_mask(pb_ctx *ctx, const float *x, const float *y, const float *grad0_x,
                  const float *grad0_y, float *out, int B, int C, int H, int W);

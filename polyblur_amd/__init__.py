@@ -6,6 +6,9 @@ The compute path is hand-written HIP for gfx950 behind the C ABI in
 first call.  There is no CPU fallback: without the library or a GPU the calls raise.
 """
 from .deblurring import polyblur_deblurring, polyblur_deblurring_uint8, PolyblurDeblurring  # noqa: F401
+# the non-blind step with a kernel of the caller's (reference deblurring.py:211-239, filters.py:14-37, edgetaper.py:26-33)
+from .nonblind import inverse_filtering_rank3, convolve2d, edgetaper  # noqa: F401
 
-__all__ = ["polyblur_deblurring", "polyblur_deblurring_uint8", "PolyblurDeblurring"]
+__all__ = ["polyblur_deblurring", "polyblur_deblurring_uint8", "PolyblurDeblurring",
+           "inverse_filtering_rank3", "convolve2d", "edgetaper"]
 __version__ = "0.1.0"

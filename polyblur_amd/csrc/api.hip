@@ -2,6 +2,7 @@
 // drivers that chain the kernels of conv.hip / estimate.hip / filters.hip on one stream.
 // Mirrors polyblur_deblurring's main loop (reference deblurring.py:58-96) and
 // inverse_filtering_rank3 (deblurring.py:211-239).
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -262,9 +263,9 @@ struct Geometry {
     float *sep_u = nullptr;
     // pb_options.half_temporaries: the two Horner temporaries are stored as fp16 (fp32 accumulation, fp32 x operand)
     void *t1h = nullptr, *t2h = nullptr;
-    // ker_size above 25: the taps on the ker_size grid (conv_big.hip), rebuilt after every estimation
-    const float *big_taps = nullptr;
-    int big_ksize = 0;
+    // ker_size above 25: the taps on the ker_size grid (conv_big.hip), rebuilt after every estimation; a caller's kernel set
+    // beyond the 25 x 25 record (pb_taps): its table for the call's boundary
+    BigTaps big;
     // the records are point-symmetric Gaussians the estimation of THIS call builds on an odd ker_size grid (PolySpec.always)
     bool est_gaussians = false;
     // ... and every one of them takes the window form of a single pass (PolySpec.always == 2): the edgetaper's three blends
@@ -316,15 +317,15 @@ int run_edgetaper(pb_ctx *ctx, const Geometry &g, const void *src, int src_dtype
     set_in_virtual(p, g, src, src_dtype);
     set_x_virtual(p, g, src, src_dtype);
     set_out_padded(p, g, pa);
-    if (g.big_taps) {
+    if (g.big.taps) {
         // (a kernel beyond the 25 x 25 record: the three blends through conv_big.hip's pass, weights from its own autocorrelations)
-        int rcb = pb_launch_conv_big(ctx, p, g.big_taps, g.big_ksize);
+        int rcb = pb_launch_conv_big(ctx, p, g.big);
         if (rcb) return rcb;
         set_in_padded(p, g, pa); set_x_padded(p, g, pa); set_out_padded(p, g, pb);
-        rcb = pb_launch_conv_big(ctx, p, g.big_taps, g.big_ksize);
+        rcb = pb_launch_conv_big(ctx, p, g.big);
         if (rcb) return rcb;
         set_in_padded(p, g, pb); set_x_padded(p, g, pb); set_out_padded(p, g, pa);
-        rcb = pb_launch_conv_big(ctx, p, g.big_taps, g.big_ksize);
+        rcb = pb_launch_conv_big(ctx, p, g.big);
         *result = pa;
         return rcb;
     }
@@ -435,9 +436,9 @@ int run_polynomial(pb_ctx *ctx, const Geometry &g, const void *xsrc, int x_dtype
     }
     ConvPass steps[3];
     make_steps(g, xsrc, x_dtype, xpadded, info, alpha, beta, boundary, t1, t2, dst, dst_dtype, clamp01, steps);
-    if (g.big_taps) {
+    if (g.big.taps) {
         for (int s = 0; s < 3; ++s) {
-            const int rc = pb_launch_conv_big(ctx, steps[s], g.big_taps, g.big_ksize);
+            const int rc = pb_launch_conv_big(ctx, steps[s], g.big);
             if (rc) return rc;
         }
         return PB_OK;
@@ -485,6 +486,28 @@ int inverse_filter(pb_ctx *ctx, const Geometry &g, const void *src, int src_dtyp
     if (!y) return PB_ERR_NOMEM;
     int rc = run_polynomial(ctx, g, src, src_dtype, xpadded, info, alpha, beta, boundary, t1, t2, y, PB_F32, 0);
     if (rc) return rc;
+    if (!g0x) {
+        // grad_img=None (deblurring.py:200-201): the gradients of the image the halo mask blends with -- the crop of the
+        // padded plane, AFTER the edgetaper where there is one (:237)
+        float *x32 = static_cast<float *>(pb_scratch(ctx, "inv.x32", sizeof(float) * g.P * g.HW));
+        float *gx = static_cast<float *>(pb_scratch(ctx, "inv.g0x", sizeof(float) * g.P * g.HW));
+        float *gy = static_cast<float *>(pb_scratch(ctx, "inv.g0y", sizeof(float) * g.P * g.HW));
+        float *e = static_cast<float *>(pb_scratch(ctx, "inv.nM", sizeof(float) * g.P));
+        if (!x32 || !gx || !gy || !e) return PB_ERR_NOMEM;
+        if (xpadded) {
+            for (int pl = 0; pl < g.P; ++pl)
+                PB_HIP(hipMemcpy2DAsync(x32 + pl * g.HW, sizeof(float) * g.W, xpadded + pl * g.pplane + (long)g.pad * g.pp + g.pad,
+                                        sizeof(float) * g.pp, sizeof(float) * g.W, g.H, hipMemcpyDeviceToDevice, ctx->stream));
+        } else if (src_dtype != PB_F32) {
+            rc = pb_convert_to_float(ctx, src, src_dtype, x32, g.P * g.HW);
+            if (rc) return rc;
+        }
+        rc = pb_fourier_gradients_impl(ctx, (xpadded || src_dtype != PB_F32) ? x32 : static_cast<const float *>(src), g.P, g.H, g.W, gx, gy);
+        if (rc) return rc;
+        rc = pb_grad_energy(ctx, gx, gy, e, g.P, g.HW);
+        if (rc) return rc;
+        g0x = gx; g0y = gy; nM = e; g_dtype = PB_F32;
+    }
     void *ox = pb_scratch(ctx, "inv.ox", dsize(g_dtype) * g.P * g.HW);    // (in the type of grad_img's planes)
     if (!ox) return PB_ERR_NOMEM;
     rc = pb_fourier_gradients_typed(ctx, y, g.P, g.H, g.W, ox, nullptr, g_dtype);     // only gout_x is used (deblurring.py:174)
@@ -868,9 +891,8 @@ int pb_polyblur_batch(pb_ctx *ctx, const void *in, void *out, int dtype, int B, 
         ctx->poly_want = no_poly(); ctx->poly_want2 = no_poly();
         if (rc) return rc;
         if (ksize > PB_KSIZE) {
-            rc = pb_build_big_taps(ctx, info, B, ksize, (!(ksize & 1) && opt->boundary == PB_WRAP) ? 1 : 0, &g.big_taps);
+            rc = pb_build_big_taps(ctx, info, B, ksize, (!(ksize & 1) && opt->boundary == PB_WRAP) ? 1 : 0, &g.big);
             if (rc) return rc;
-            g.big_ksize = ksize;
         }
         if (sep) {
             rc = pb_make_sep_records(ctx, B, info, sep, opt->support, ksize);
@@ -1017,6 +1039,211 @@ int pb_time_inner_loop(pb_ctx *ctx, const void *in, void *out, int dtype, int B,
     PB_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     *host_ms = ms / reps;
     return PB_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// caller-owned kernel sets: the non-blind entry points for any kh x kw taps up to 49 x 49
+// (deblurring.py:211-239, filters.py:14-37, edgetaper.py:26-33 with a kernel tensor of the caller's)
+// ---------------------------------------------------------------------------------------------
+// Either 25 x 25 records every body of the reblurring pass serves (kh, kw <= 25, not taller than wide) or conv_big.hip's tap
+// tables; either way one form for the zero boundary (correlation placed by the 'same' rule) and one for the wrap boundary (the
+// taps reflected inside their own kh x kw array, THEN placed -- reflecting an embedded even-sized array is off by one
+// sample).  All of it is device memory of the set's own: no other call on the context touches it.
+struct pb_taps {
+    pb_ctx *ctx = nullptr;
+    int B = 0, kh = 0, kw = 0;
+    pb_blur_info *rec_zero = nullptr, *rec_wrap = nullptr;      // records (rec_wrap == rec_zero: point-symmetric as embedded)
+    float *tables = nullptr;                                    // tables: B zero-boundary ones, B wrap-boundary ones, B autocorrelations
+    BigTaps big_zero, big_wrap;
+};
+
+namespace {
+
+bool taps_in_records(int kh, int kw) { return kh <= PB_KSIZE && kw <= PB_KSIZE && kh / 2 <= kw / 2; }
+
+// kh x kw taps into a zeroed 25 x 25 array: tap (i, j) at row 12 - (kh - 1) / 2 + i, column 12 - (kw - 1) / 2 + j
+void embed_taps(const float *k, int kh, int kw, bool reflect, float *rec) {
+    const int r0 = PB_KRAD - (kh - 1) / 2, c0 = PB_KRAD - (kw - 1) / 2;
+    for (int i = 0; i < kh; ++i)
+        for (int j = 0; j < kw; ++j)
+            rec[(r0 + i) * PB_KSIZE + c0 + j] = reflect ? k[(kh - 1 - i) * kw + (kw - 1 - j)] : k[i * kw + j];
+}
+
+int taps_records(pb_ctx *ctx, const float *host_taps, int B, int kh, int kw, bool reflect, int support, pb_blur_info *rec) {
+    std::vector<pb_blur_info> h(B);
+    memset(h.data(), 0, sizeof(pb_blur_info) * B);
+    for (int i = 0; i < B; ++i) embed_taps(host_taps + (size_t)i * kh * kw, kh, kw, reflect, h[i].kernel);
+    PB_HIP(hipMemcpyAsync(rec, h.data(), sizeof(pb_blur_info) * B, hipMemcpyHostToDevice, ctx->stream));
+    PB_HIP(hipStreamSynchronize(ctx->stream));
+    const int rc = pb_make_kernels_dev(ctx, B, rec, support, 1);
+    return rc ? rc : pb_cache_records(ctx, rec, B);
+}
+
+// what every call with a set checks, and the geometry + records it then runs with.  domain: the given image is the whole
+// domain (pb_convolve2d_taps, pb_edgetaper_taps) -- no pad; else the image is replicate-padded by kw / 2 (utils.py:48-61: the
+// height of the kernel plays no part)
+int taps_geometry(pb_ctx *ctx, const pb_taps *t, int B, int C, int H, int W, int boundary, bool domain, bool circular_only,
+                  Geometry *g, const pb_blur_info **recs) {
+    if (!t || t->ctx != ctx) return pb_fail(ctx, PB_ERR_BADARG, "the kernel set is not one of this context's");
+    if (boundary != PB_WRAP && boundary != PB_ZERO) return pb_fail(ctx, PB_ERR_BADARG, "bad boundary");
+    if (t->B != B) return pb_fail(ctx, PB_ERR_BADARG, "the set holds %d kernels, the batch %d images (one kernel per image)", t->B, B);
+    const int pad = domain ? 0 : t->kw / 2;
+    if (t->kh > H + 2 * pad - 1)
+        return pb_fail(ctx, PB_ERR_BADARG, "a kernel of %d rows does not fit the %d rows of the %sdomain (at most rows - 1: filters.py:255-273, edgetaper.py:11)",
+                       t->kh, H + 2 * pad, domain ? "" : "padded ");
+    if (t->kw > W + 2 * pad - 1)
+        return pb_fail(ctx, PB_ERR_BADARG, "a kernel of %d columns does not fit the %d columns of the domain (at most columns - 1)", t->kw, W + 2 * pad);
+    if (circular_only && boundary == PB_WRAP && t->kh / 2 > t->kw / 2)
+        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "a %d x %d kernel is taller than wide: convolve2d(method='fft') pads circularly by the half-WIDTH only "
+                       "(filters.py:33, utils.py:48-61), which is no circular convolution over the domain -- not built", t->kh, t->kw);
+    *g = geometry(B, C, H, W, pad);
+    if (t->tables) { g->big = boundary == PB_WRAP ? t->big_wrap : t->big_zero; *recs = nullptr; }      // (conv_big.hip reads no record)
+    else *recs = boundary == PB_WRAP ? t->rec_wrap : t->rec_zero;
+    return PB_OK;
+}
+
+int taps_pass(pb_ctx *ctx, const Geometry &g, const ConvPass &p) { return g.big.taps ? pb_launch_conv_big(ctx, p, g.big) : pb_launch_conv(ctx, p); }
+
+}  // namespace
+
+extern "C" {
+
+int pb_taps_create(pb_ctx *ctx, int B, int kh, int kw, const float *host_taps, int support, pb_taps **taps) {
+    if (!ctx || !taps) return PB_ERR_BADARG;
+    *taps = nullptr;
+    if (B < 1 || !host_taps) return pb_fail(ctx, PB_ERR_BADARG, "pb_taps_create: bad argument");
+    if (kh < 1 || kw < 1) return pb_fail(ctx, PB_ERR_BADARG, "a %d x %d kernel: sizes start at 1 x 2", kh, kw);
+    if (kw == 1) return pb_fail(ctx, PB_ERR_BADARG, "a kernel one tap wide pads by 0 samples, and the reference's crop [0:-0] is then empty (utils.py:63-67)");
+    if (kh > PB_KSIZE_MAX || kw > PB_KSIZE_MAX)
+        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "a %d x %d kernel: sizes up to %d x %d are built", kh, kw, PB_KSIZE_MAX, PB_KSIZE_MAX);
+    PB_HIP(hipSetDevice(ctx->device));
+    pb_taps *t = new pb_taps();
+    t->ctx = ctx; t->B = B; t->kh = kh; t->kw = kw;
+    int rc = PB_OK;
+    if (taps_in_records(kh, kw)) {
+        bool sym = true;                                     // (as embedded: an even size never is)
+        std::vector<float> e(PB_KSIZE * PB_KSIZE);
+        for (int i = 0; i < B && sym; ++i) {
+            std::fill(e.begin(), e.end(), 0.f);
+            embed_taps(host_taps + (size_t)i * kh * kw, kh, kw, false, e.data());
+            for (int n = 0; n < PB_KSIZE * PB_KSIZE / 2 && sym; ++n) sym = e[n] == e[PB_KSIZE * PB_KSIZE - 1 - n];
+        }
+        void *m = nullptr;
+        if (hipMalloc(&m, sizeof(pb_blur_info) * (size_t)B * (sym ? 1 : 2)) != hipSuccess) {
+            delete t;
+            return pb_fail(ctx, PB_ERR_NOMEM, "pb_taps_create: hipMalloc of %d records failed", B * (sym ? 1 : 2));
+        }
+        t->rec_zero = static_cast<pb_blur_info *>(m);
+        t->rec_wrap = sym ? t->rec_zero : t->rec_zero + B;
+        rc = taps_records(ctx, host_taps, B, kh, kw, false, support, t->rec_zero);
+        if (!rc && !sym) rc = taps_records(ctx, host_taps, B, kh, kw, true, support, t->rec_wrap);
+    } else {
+        const size_t nt = (size_t)PB_BIG_TABLE * B;
+        void *m = nullptr;
+        if (hipMalloc(&m, sizeof(float) * (2 * nt + (size_t)PB_BIG_ACORR * B)) != hipSuccess) {
+            delete t;
+            return pb_fail(ctx, PB_ERR_NOMEM, "pb_taps_create: hipMalloc of %d tap tables failed", 2 * B);
+        }
+        t->tables = static_cast<float *>(m);
+        float *raw = static_cast<float *>(pb_scratch(ctx, "taps.raw", sizeof(float) * (size_t)B * kh * kw));   // (only until the tables are built)
+        rc = raw ? PB_OK : PB_ERR_NOMEM;
+        if (!rc && hipMemcpyAsync(raw, host_taps, sizeof(float) * (size_t)B * kh * kw, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+            rc = pb_fail(ctx, PB_ERR_HIP, "pb_taps_create: copy of the taps failed");
+        if (!rc) rc = pb_build_caller_taps(ctx, raw, B, kh, kw, t->tables, t->tables + nt, t->tables + 2 * nt);
+        if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = pb_fail(ctx, PB_ERR_HIP, "pb_taps_create: building the tap tables failed");
+        t->big_zero.taps = t->tables; t->big_wrap.taps = t->tables + nt;
+        t->big_zero.acorr = t->big_wrap.acorr = t->tables + 2 * nt;
+        t->big_zero.ry = t->big_wrap.ry = kh / 2;
+        t->big_zero.rx = t->big_wrap.rx = kw / 2;
+    }
+    if (rc) { (void)pb_taps_free(t); return rc; }
+    *taps = t;
+    return PB_OK;
+}
+
+int pb_taps_free(pb_taps *t) {
+    if (!t) return PB_OK;
+    pb_ctx *ctx = t->ctx;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    if (t->rec_zero) {
+        pb_forget_records(ctx, t->rec_zero, t->rec_wrap == t->rec_zero ? t->B : 2 * t->B);      // (the address may come back with other taps)
+        (void)hipFree(t->rec_zero);
+    }
+    if (t->tables) (void)hipFree(t->tables);
+    delete t;
+    return PB_OK;
+}
+
+int pb_convolve2d_taps(pb_ctx *ctx, const float *in, float *out, int B, int C, int H, int W, const pb_taps *taps, int boundary) {
+    int rc = check_shape(ctx, PB_F32, B, C, H, W);
+    if (rc) return rc;
+    if (!in || !out || in == out) return pb_fail(ctx, PB_ERR_BADARG, "null or aliased image");
+    Geometry g; const pb_blur_info *recs = nullptr;
+    rc = taps_geometry(ctx, taps, B, C, H, W, boundary, true, true, &g, &recs);
+    if (rc) return rc;
+    PB_HIP(hipSetDevice(ctx->device));
+    g.pp = W; g.pplane = g.HW;                              // (the caller's planes are not pitched)
+    ConvPass p = base_pass(g, recs, boundary);
+    set_in_padded(p, g, in); set_x_padded(p, g, in); set_out_padded(p, g, out);
+    return taps_pass(ctx, g, p);
+}
+
+int pb_edgetaper_taps(pb_ctx *ctx, const float *in, float *out, int B, int C, int H, int W, const pb_taps *taps, int boundary,
+                      int n_tapers) {
+    int rc = check_shape(ctx, PB_F32, B, C, H, W);
+    if (rc) return rc;
+    if (!in || !out || in == out) return pb_fail(ctx, PB_ERR_BADARG, "null or aliased image");
+    if (n_tapers < 0) return pb_fail(ctx, PB_ERR_BADARG, "n_tapers < 0");
+    Geometry g; const pb_blur_info *recs = nullptr;
+    rc = taps_geometry(ctx, taps, B, C, H, W, boundary, true, true, &g, &recs);
+    if (rc) return rc;
+    PB_HIP(hipSetDevice(ctx->device));
+    g.pp = W; g.pplane = g.HW;
+    if (n_tapers == 0) {
+        PB_HIP(hipMemcpyAsync(out, in, sizeof(float) * g.P * g.HW, hipMemcpyDeviceToDevice, ctx->stream));
+        return PB_OK;
+    }
+    float *tmp = nullptr;
+    if (n_tapers > 1) {
+        tmp = static_cast<float *>(pb_scratch(ctx, "taper.tmp", sizeof(float) * g.P * g.HW));
+        if (!tmp) return PB_ERR_NOMEM;
+    }
+    ConvPass p = base_pass(g, recs, boundary);
+    p.epilogue = EPI_TAPER;
+    // (the blends alternate between `out` and the scratch plane so that the last one lands in `out`)
+    const float *src = in;
+    for (int i = 0; i < n_tapers; ++i) {
+        float *dst = ((n_tapers - 1 - i) & 1) ? tmp : out;
+        set_in_padded(p, g, src); set_x_padded(p, g, src); set_out_padded(p, g, dst);
+        rc = taps_pass(ctx, g, p);
+        if (rc) return rc;
+        src = dst;
+    }
+    return PB_OK;
+}
+
+int pb_inverse_filter_taps(pb_ctx *ctx, const void *in, void *out, int dtype, int B, int C, int H, int W, const pb_taps *taps,
+                           float alpha, float beta, int boundary, int edgetaping, int remove_halo, const float *grad0_x,
+                           const float *grad0_y) {
+    int rc = check_shape(ctx, dtype, B, C, H, W);
+    if (rc) return rc;
+    if (!in || !out || in == out) return pb_fail(ctx, PB_ERR_BADARG, "null or aliased image");
+    if ((grad0_x == nullptr) != (grad0_y == nullptr)) return pb_fail(ctx, PB_ERR_BADARG, "grad0_x and grad0_y: both or neither");
+    Geometry g; const pb_blur_info *recs = nullptr;
+    rc = taps_geometry(ctx, taps, B, C, H, W, boundary, false, edgetaping != 0, &g, &recs);
+    if (rc) return rc;
+    PB_HIP(hipSetDevice(ctx->device));
+    float *nM = nullptr;
+    if (remove_halo && grad0_x) {
+        nM = static_cast<float *>(pb_scratch(ctx, "inv.nM", sizeof(float) * g.P));
+        if (!nM) return PB_ERR_NOMEM;
+        rc = pb_grad_energy(ctx, grad0_x, grad0_y, nM, g.P, g.HW);
+        if (rc) return rc;
+    }
+    return inverse_filter(ctx, g, in, dtype, out, dtype, recs, alpha, beta, boundary, edgetaping, remove_halo, grad0_x, grad0_y, nM, 1);
 }
 
 }  // extern "C"

@@ -305,9 +305,17 @@ bool pb_conv_w128_types(int in_dtype, int out_dtype);                           
 bool pb_poly_three_steps_ok(pb_ctx *ctx, const ConvPass *steps);             // conv.hip: the three steps can all take the wave form (PolySpec.always == 2)
 int pb_poly_spec_mode(pb_ctx *ctx, const ConvPass *steps);                   // conv.hip: the PolySpec.on a polynomial with these steps may ask for
 // kernels larger than the 25 x 25 record (conv_big.hip): their taps on the ker_size grid, and one Horner step with them
-int pb_build_big_taps(pb_ctx *ctx, const pb_blur_info *dev_info, int B, int ksize, int shift, const float **taps);
-int pb_launch_conv_big(pb_ctx *ctx, const ConvPass &p, const float *taps, int ksize);
+// BigTaps: one table of PB_BIG_TABLE floats per image (49 rows of 56: entry [iy + 24][ix + 24] multiplies the sample (iy, ix) away
+// from the output, zero outside the support), PB_BIG_ACORR floats of autocorrelations per image (the edgetaper's weights), and
+// the half-sizes the pass walks: kernel rows -ry .. ry, taps -rx .. rx of each
 constexpr int PB_KSIZE_MAX = 49;
+constexpr int PB_BIG_TABLE = PB_KSIZE_MAX * 56, PB_BIG_ACORR = 2 * 64;
+struct BigTaps { const float *taps = nullptr, *acorr = nullptr; int ry = 0, rx = 0; };
+int pb_build_big_taps(pb_ctx *ctx, const pb_blur_info *dev_info, int B, int ksize, int shift, BigTaps *big);
+// the same tables from a caller's kh x kw taps (B * kh * kw floats on the device): `zero` placed by F.conv2d's 'same' rule,
+// `wrap` the taps reflected inside their own array, then placed by p2o's roll; `acorr` serves both
+int pb_build_caller_taps(pb_ctx *ctx, const float *dev_raw, int B, int kh, int kw, float *zero, float *wrap, float *acorr);
+int pb_launch_conv_big(pb_ctx *ctx, const ConvPass &p, const BigTaps &big);
 bool pb_conv_fft_feasible(const ConvPass &p);                                // window counts within the kernel's index arithmetic
 
 // ------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import threading
+import weakref
 
 import numpy as np
 
@@ -50,6 +51,34 @@ class DeviceBuffer:
             pass
 
 
+class KernelSet:
+    """A caller's kernels on the device (pb_taps): B kernels of kh x kw taps, owned by this object and not by the engine's
+    scratch -- it survives any other call on the engine and is released by free() (or with the object)."""
+
+    def __init__(self, engine: "Engine", taps: np.ndarray, support: int = capi.PB_SUPPORT_FULL):
+        k = np.ascontiguousarray(taps, np.float32)
+        if k.ndim != 3:
+            raise ValueError("expected (B, kh, kw) taps, got shape %r" % (k.shape,))
+        self.engine = engine
+        self.B, self.kh, self.kw = (int(v) for v in k.shape)
+        h = C.c_void_p()
+        engine._check(engine.lib.pb_taps_create(engine.ctx, self.B, self.kh, self.kw, k.ctypes.data_as(C.POINTER(C.c_float)),
+                                                int(support), C.byref(h)))
+        self.handle = h
+        engine._sets.add(self)
+
+    def free(self):
+        if self.handle and self.engine.ctx:                  # (a closed engine has taken the device memory with it)
+            self.engine.lib.pb_taps_free(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Engine:
     def __init__(self, device: int = 0, stream: int | None = None):
         self.lib = capi.load_library()
@@ -61,6 +90,7 @@ class Engine:
         self.ctx = ctx
         self.device = device
         self._pool = {}
+        self._sets = weakref.WeakSet()       # live KernelSets: their device memory goes before the context does
 
     # ---- infrastructure ------------------------------------------------------------------
     def _check(self, rc: int):
@@ -73,6 +103,8 @@ class Engine:
             for b in self._pool.values():
                 b.free()
             self._pool.clear()
+            for ks in list(self._sets):
+                ks.free()
             self.lib.pb_destroy(self.ctx)
             self.ctx = None
 
@@ -241,6 +273,52 @@ class Engine:
         self._check(self.lib.pb_edgetaper(self.ctx, din.ptr, dout.ptr, B, Cc, Hp, Wp, info.ptr, int(boundary)))
         self.synchronize()
         return dout.download(xp.shape, np.float32)
+
+    # ---- caller-owned kernel sets (pb_taps): any kh x kw up to 49 x 49 ---------------------
+    def set_taps(self, taps, support=capi.PB_SUPPORT_FULL) -> KernelSet:
+        """(B, kh, kw) taps -> a KernelSet; the caller frees it (KernelSet.free) before the engine is closed."""
+        return KernelSet(self, taps, support)
+
+    def convolve2d_taps_ptr(self, in_ptr: int, out_ptr: int, shape, ks: KernelSet, boundary=capi.PB_ZERO):
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_convolve2d_taps(self.ctx, in_ptr, out_ptr, B, Cc, H, W, ks.handle, int(boundary)))
+
+    def edgetaper_taps_ptr(self, in_ptr: int, out_ptr: int, shape, ks: KernelSet, boundary=capi.PB_WRAP, n_tapers=3):
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_edgetaper_taps(self.ctx, in_ptr, out_ptr, B, Cc, H, W, ks.handle, int(boundary), int(n_tapers)))
+
+    def inverse_filter_taps_ptr(self, in_ptr: int, out_ptr: int, dtype: int, shape, ks: KernelSet, alpha, beta,
+                                boundary=capi.PB_ZERO, edgetaping=False, remove_halo=False, g0x_ptr=None, g0y_ptr=None):
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_inverse_filter_taps(self.ctx, in_ptr, out_ptr, dtype, B, Cc, H, W, ks.handle, float(alpha),
+                                                    float(beta), int(boundary), int(bool(edgetaping)), int(bool(remove_halo)),
+                                                    g0x_ptr, g0y_ptr))
+
+    def _taps_call(self, x: np.ndarray, call):
+        x = np.ascontiguousarray(x)
+        din = self.to_device("np.in", x)
+        dout = self.buffer("np.out", x.nbytes)
+        call(din.ptr, dout.ptr)
+        self.synchronize()
+        return dout.download(x.shape, x.dtype)
+
+    def convolve2d_taps(self, x: np.ndarray, ks: KernelSet, boundary=capi.PB_ZERO) -> np.ndarray:
+        x = np.ascontiguousarray(x, np.float32)
+        return self._taps_call(x, lambda i, o: self.convolve2d_taps_ptr(i, o, x.shape, ks, boundary))
+
+    def edgetaper_taps(self, x: np.ndarray, ks: KernelSet, boundary=capi.PB_WRAP, n_tapers=3) -> np.ndarray:
+        x = np.ascontiguousarray(x, np.float32)
+        return self._taps_call(x, lambda i, o: self.edgetaper_taps_ptr(i, o, x.shape, ks, boundary, n_tapers))
+
+    def inverse_filter_taps(self, x: np.ndarray, ks: KernelSet, alpha, beta, boundary=capi.PB_ZERO, edgetaping=False,
+                            remove_halo=False, grad0=None) -> np.ndarray:
+        x = np.ascontiguousarray(x)
+        g0x = g0y = None
+        if remove_halo and grad0 is not None:
+            g0x = self.to_device("np.g0x", np.ascontiguousarray(grad0[0], np.float32)).ptr
+            g0y = self.to_device("np.g0y", np.ascontiguousarray(grad0[1], np.float32)).ptr
+        return self._taps_call(x, lambda i, o: self.inverse_filter_taps_ptr(i, o, _DT[x.dtype], x.shape, ks, alpha, beta, boundary,
+                                                                            edgetaping, remove_halo, g0x, g0y))
 
     def halo_mask(self, x, y, g0x, g0y) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)

@@ -1,0 +1,189 @@
+"""The reference's non-blind functions with a kernel of the caller's (deblurring.py:211-239, filters.py:14-37,
+edgetaper.py:26-33):
+
+    from polyblur_amd import inverse_filtering_rank3, convolve2d, edgetaper
+
+Same names, arguments and defaults.  ``img`` is a (B,C,H,W) ``torch.Tensor`` -- on a ROCm device (used in place, on torch's
+current stream) or on the CPU (staged through the GPU) -- or an ``np.ndarray`` of that shape; float32, or float16 for the
+inverse filter.  The result has the type and device of ``img``.  ``kernel`` is a (B,1,h,w) tensor or array -- one kernel per
+image --, (B,C,h,w) -- one per plane --, or either with a batch of 1, which broadcasts; 1 <= h <= 49, 2 <= w <= 49, even, odd,
+square or rectangular, taps used as given.
+
+``method`` is the boundary model, as in the blind driver: 'direct' = F.conv2d(padding='same'), zero outside the padded
+domain; 'fft' = circular convolution over it with the PSF rolled by -(h//2), -(w//2).  Under 'direct' the reference itself
+fails for per-plane kernels and for B > 1 (filters.py:45-49); here every plane gets its own correlation.
+
+Refused before any device work: a kernel one tap wide (the reference's crop [0:-0] is empty) and one that does not fit the
+domain (ValueError); sides above 49, tuple kernels / method='direct_separable', and -- in convolve2d, edgetaper and
+do_edgetaper=True under 'fft' -- a kernel taller than wide, for which the reference's circular pad by the half-width is no
+circular convolution over the domain (NotImplementedError).
+
+The arithmetic is the HIP engine's (include/polyblur_hip.h: pb_taps_create and the three *_taps calls); nothing runs on the CPU.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _capi as capi
+from .deblurring import _check_image_size, _is_torch_tensor
+from .engine import get_engine
+
+_BOUNDARY = {"fft": capi.PB_WRAP, "direct": capi.PB_ZERO}
+
+
+def _host_array(a):
+    return a.detach().cpu().numpy() if _is_torch_tensor(a) else np.asarray(a)
+
+
+def _check_image(img, allow_half):
+    """-> (is_tensor, shape, numpy dtype) of a (B,C,H,W) image."""
+    if _is_torch_tensor(img):
+        import torch
+        if img.dim() != 4:
+            raise ValueError("expected a (B,C,H,W) tensor, got shape %r" % (tuple(img.shape),))
+        if img.dtype == torch.float32:
+            dt = np.dtype(np.float32)
+        elif img.dtype == torch.float16 and allow_half:
+            dt = np.dtype(np.float16)
+        else:
+            raise TypeError("tensor dtype must be float32%s" % (" or float16" if allow_half else ""))
+        shape = tuple(int(v) for v in img.shape)
+        tensor = True
+    elif isinstance(img, np.ndarray):
+        if img.ndim != 4:
+            raise ValueError("expected a (B,C,H,W) array, got shape %r" % (img.shape,))
+        dt = np.dtype(np.float16) if (img.dtype == np.float16 and allow_half) else np.dtype(np.float32)
+        shape = tuple(int(v) for v in img.shape)
+        tensor = False
+    else:
+        raise TypeError("img must be a numpy.ndarray or a torch.Tensor")
+    if shape[0] < 1 or shape[1] < 1 or shape[2] < 2 or shape[3] < 2:
+        raise ValueError("bad image shape %r" % (shape,))
+    return tensor, shape, dt
+
+
+def _check_kernel(kernel, method, img_shape, pad_domain, circular_only, correlate=False):
+    """Every refusal, then the taps as (B', kh, kw) float32 with B' = B (one kernel per image) or B*C (one per plane; the
+    image is then passed as B*C one-channel images) -> (taps, per_plane)."""
+    if isinstance(kernel, (tuple, list)):
+        raise NotImplementedError("tuple kernels (the separable 1-D form, filters.py:29-30) are not built: pass a (B,C,h,w) kernel")
+    if method == "direct_separable":
+        raise NotImplementedError("method='direct_separable' takes tuple kernels, which are not built here")
+    if method not in _BOUNDARY:
+        raise ValueError("%s not implemented" % method)
+    if not (_is_torch_tensor(kernel) or isinstance(kernel, np.ndarray)):
+        raise TypeError("kernel must be a numpy.ndarray or a torch.Tensor")
+    if len(kernel.shape) != 4:
+        raise ValueError("expected a (B,C,h,w) kernel, got shape %r" % (tuple(kernel.shape),))
+    B, C, H, W = img_shape
+    kb, kc, kh, kw = (int(v) for v in kernel.shape)
+    if kb not in (1, B) or kc not in (1, C):
+        raise ValueError("kernel shape %r does not match the image's (%d,%d,...): batch 1 or %d, channels 1 or %d"
+                         % (tuple(kernel.shape), B, C, B, C))
+    if kh < 1 or kw < 1:
+        raise ValueError("empty kernel")
+    if kw == 1:
+        raise ValueError("a kernel one tap wide pads by 0 samples and the reference's crop [0:-0] is then empty")
+    if kh > capi.PB_KSIZE_MAX or kw > capi.PB_KSIZE_MAX:
+        raise NotImplementedError("a %d x %d kernel: sides up to %d are built" % (kh, kw, capi.PB_KSIZE_MAX))
+    pad = kw // 2 if pad_domain else 0
+    if kh > H + 2 * pad - 1 or kw > W + 2 * pad - 1:
+        raise ValueError("a %d x %d kernel does not fit the %d x %d domain (at most rows - 1, columns - 1)"
+                         % (kh, kw, H + 2 * pad, W + 2 * pad))
+    if circular_only and method == "fft" and kh // 2 > kw // 2:
+        raise NotImplementedError("a kernel taller than wide under method='fft': the reference pads circularly by the "
+                                  "half-width only, which is no circular convolution over the domain -- not built")
+    k = np.asarray(_host_array(kernel), np.float32)
+    if correlate:
+        k = k[..., ::-1, ::-1]                              # torch.rot90(kernel, 2, (-2, -1)), deblurring.py:225-226
+    per_plane = kc > 1
+    k = np.broadcast_to(k, (B, kc, kh, kw))
+    return np.ascontiguousarray(k).reshape(B * kc, kh, kw), per_plane
+
+
+def _run(img, tensor, dt, shape, taps, per_plane, call, extra=()):
+    """call(engine, kernel set, in_ptr, out_ptr, shape, extra_ptrs) on the right stream; `extra`: further (B,C,H,W) float32
+    operands (tensors or arrays) the call reads."""
+    B, C, H, W = shape
+    eshape = (B * C, 1, H, W) if per_plane else shape
+    if tensor and img.is_cuda:
+        import torch
+        dev = img.device.index if img.device.index is not None else torch.cuda.current_device()
+        eng = get_engine(dev)
+        xin = img.contiguous()
+        out = torch.empty_like(xin)
+        ex = [torch.as_tensor(e, dtype=torch.float32, device=img.device).contiguous() for e in extra]
+        with torch.cuda.device(dev):
+            eng.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+            ks = eng.set_taps(taps)
+            try:
+                call(eng, ks, xin.data_ptr(), out.data_ptr(), eshape, [e.data_ptr() for e in ex])
+            finally:
+                ks.free()                                   # (waits for the stream: the set is in use until then)
+        return out
+    eng = get_engine(0)
+    eng.set_stream(0)
+    x = np.ascontiguousarray(_host_array(img), dtype=dt)
+    din = eng.to_device("np.in", x)
+    dout = eng.buffer("np.out", x.nbytes)
+    ex = [eng.to_device("np.g0%s" % "xy"[i], np.ascontiguousarray(_host_array(e), np.float32)).ptr for i, e in enumerate(extra)]
+    ks = eng.set_taps(taps)
+    try:
+        call(eng, ks, din.ptr, dout.ptr, eshape, ex)
+        eng.synchronize()
+    finally:
+        ks.free()
+    out = dout.download(x.shape, x.dtype)
+    if tensor:
+        import torch
+        return torch.from_numpy(out)
+    return out
+
+
+def convolve2d(img, kernel, method='direct'):
+    """filters.convolve2d (filters.py:14-37) with a 2-D kernel: ``img`` is the whole domain."""
+    tensor, shape, dt = _check_image(img, allow_half=False)
+    taps, per_plane = _check_kernel(kernel, method, shape, pad_domain=False, circular_only=True)
+    bnd = _BOUNDARY[method]
+    return _run(img, tensor, dt, shape, taps, per_plane,
+                lambda eng, ks, i, o, s, ex: eng.convolve2d_taps_ptr(i, o, s, ks, bnd))
+
+
+def edgetaper(img, kernel, n_tapers=3, method='fft'):
+    """edgetaper.edgetaper (edgetaper.py:26-33): ``n_tapers`` blends of ``img`` with its blurred self, weighted by the
+    autocorrelations of the kernel's projections."""
+    tensor, shape, dt = _check_image(img, allow_half=False)
+    if not isinstance(n_tapers, (int, np.integer)) or n_tapers < 0:
+        raise ValueError("n_tapers must be an integer >= 0")
+    taps, per_plane = _check_kernel(kernel, method, shape, pad_domain=False, circular_only=True)
+    bnd = _BOUNDARY[method]
+    return _run(img, tensor, dt, shape, taps, per_plane,
+                lambda eng, ks, i, o, s, ex: eng.edgetaper_taps_ptr(i, o, s, ks, bnd, int(n_tapers)))
+
+
+def inverse_filtering_rank3(img, kernel, alpha=2, b=4, correlate=False, remove_halo=False, do_edgetaper=False,
+                            grad_img=None, method='direct'):
+    """deblurring.inverse_filtering_rank3 (deblurring.py:211-239): replicate pad by w // 2 -> [edgetaper] -> polynomial ->
+    crop -> [halo masking] -> clamp.  ``grad_img``: (grad_x, grad_y) of the original image, or None for the gradients of
+    the (tapered) image itself."""
+    tensor, shape, dt = _check_image(img, allow_half=True)
+    taps, per_plane = _check_kernel(kernel, method, shape, pad_domain=True, circular_only=bool(do_edgetaper),
+                                    correlate=bool(correlate))
+    extra = ()
+    if remove_halo:
+        _check_image_size(*shape[-2:])
+        if grad_img is not None:
+            if not isinstance(grad_img, (tuple, list)) or len(grad_img) != 2:
+                raise ValueError("grad_img must be (grad_x, grad_y)")
+            for gpart in grad_img:
+                if tuple(int(v) for v in gpart.shape) != shape:
+                    raise ValueError("grad_img planes must have the image's shape %r" % (shape,))
+            extra = tuple(grad_img)
+    bnd = _BOUNDARY[method]
+    dtype = capi.PB_F16 if dt == np.float16 else capi.PB_F32
+
+    def call(eng, ks, i, o, s, ex):
+        eng.inverse_filter_taps_ptr(i, o, dtype, s, ks, alpha, b, bnd, bool(do_edgetaper), bool(remove_halo),
+                                    ex[0] if ex else None, ex[1] if ex else None)
+
+    return _run(img, tensor, dt, shape, taps, per_plane, call, extra)
