@@ -314,6 +314,29 @@ int pb_inverse_filter_taps(pb_ctx *ctx, const void *in, void *out, int dtype, in
                            const pb_taps *taps, float alpha, float beta, int boundary, int edgetaping,
                            int remove_halo, const float *grad0_x, const float *grad0_y);
 
+/* deblurring.compute_polynomial (deblurring.py:113-169) on a (B,C,H,W) float32 image that is the whole domain; no pad, no
+ * crop, no clamp.  not_symmetric != 0: the pure-phase filter of compute_polynomial_fft -- the image spectrum times
+ * conj(K) / (|K| + 1e-8) before the Horner steps, K = fft2(p2o(kernel)) --, PB_WRAP only (PB_ZERO -> PB_ERR_BADARG: the
+ * reference's direct form accepts the flag and ignores it; a silent no-op is refused here).  It is one transform over the whole
+ * domain: both sides need pb_fft_length_supported == 1 (PB_ERR_UNSUPPORTED otherwise).  Where |K| falls to fp32 roundoff
+ * (about 1e-7; a wide Gaussian has such bins near Nyquist) the phase of that factor is noise, in the reference as much as here.
+ * not_symmetric == 0: the existing reblurring passes over the given domain, either boundary.  A kernel taller than wide is
+ * taken (p2o is circular over the domain).  out may not alias in.                                                      */
+int pb_compute_polynomial_taps(pb_ctx *ctx, const float *in, float *out, int B, int C, int H, int W,
+                               const pb_taps *taps, float alpha, float beta, int boundary, int not_symmetric);
+
+/* inverse_filtering_rank3's chain (deblurring.py:211-239) with compute_polynomial(..., method='fft', not_symmetric=True) in
+ * the polynomial's place: replicate pad by kw / 2 -> [three edgetaper blends, PB_WRAP] -> phase-corrected polynomial -> crop
+ * -> [halo masking] -> clamp.  fp32 or fp16 images.  The argument rules and refusals of pb_inverse_filter_taps under PB_WRAP,
+ * and PB_ERR_UNSUPPORTED where a padded side has pb_fft_length_supported != 1.  out may not alias in.                   */
+int pb_inverse_filter_phase_taps(pb_ctx *ctx, const void *in, void *out, int dtype, int B, int C, int H, int W,
+                                 const pb_taps *taps, float alpha, float beta, int edgetaping, int remove_halo,
+                                 const float *grad0_x, const float *grad0_y);
+
+/* The pure-phase polynomial takes the plane pairs of an image in groups whose complex scratch (one Hp x Wp float2 plane per
+ * pair) stays within `bytes`; one pair is always allowed.  0 = the default, 256 MiB.  Results do not depend on it.       */
+int pb_set_phase_budget(pb_ctx *ctx, size_t bytes);
+
 /* halo_masking (deblurring.py:193-208), bug-compatible.  All (B,C,H,W) float32.           */
 int pb_halo_mask(pb_ctx *ctx, const float *x, const float *y, const float *grad0_x,
                  const float *grad0_y, float *out, int B, int C, int H, int W);

@@ -39,6 +39,7 @@ SYMBOLS = [
     "pb_fft_length_supported", "pb_make_separable_kernels", "pb_set_dense_eval",
     "pb_body_selection",
     "pb_taps_create", "pb_taps_free", "pb_convolve2d_taps", "pb_edgetaper_taps", "pb_inverse_filter_taps",
+    "pb_compute_polynomial_taps", "pb_inverse_filter_phase_taps", "pb_set_phase_budget",
     "pb_comm_shard", "pb_comm_unique_id", "pb_comm_init", "pb_comm_destroy", "pb_comm_scatter", "pb_comm_gather",
     "pb_comm_deblur_from_root", "pb_comm_plan_steps", "pb_comm_plan", "pb_comm_set_chunk", "pb_comm_default_chunk",
     "pb_comm_plan_steps_chunked", "pb_comm_plan_chunked",
@@ -139,6 +140,9 @@ def load_library():
             "pb_convolve2d_taps": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, ci]),
             "pb_edgetaper_taps": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, ci, ci]),
             "pb_inverse_filter_taps": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, cf, cf, ci, ci, ci, vp, vp]),
+            "pb_set_phase_budget": (ci, [vp, sz]),
+            "pb_compute_polynomial_taps": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, cf, cf, ci, ci]),
+            "pb_inverse_filter_phase_taps": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, cf, cf, ci, ci, vp, vp]),
             "pb_halo_mask": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci]),
             "pb_dt_recursive_filter": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, ci]),
             "pb_dt_normalized_convolution": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, ci]),

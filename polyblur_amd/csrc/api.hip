@@ -154,6 +154,12 @@ int pb_set_dense_eval(pb_ctx *ctx, int mode, int min_phases) {
     return PB_OK;
 }
 
+int pb_set_phase_budget(pb_ctx *ctx, size_t bytes) {
+    if (!ctx) return PB_ERR_BADARG;
+    ctx->phase_budget = bytes;
+    return PB_OK;
+}
+
 int pb_destroy(pb_ctx *ctx) {
     if (!ctx) return PB_OK;
     (void)hipSetDevice(ctx->device);
@@ -271,6 +277,9 @@ struct Geometry {
     // ... and every one of them takes the window form of a single pass (PolySpec.always == 2): the edgetaper's three blends
     // issue the wave body's launch and nothing else
     bool taper_windows = false;
+    // the polynomial is the one with the pure-phase filter (conv_phase.hip): the caller's raw kh x kw taps, one kernel per image
+    const float *phase_taps = nullptr;
+    int phase_kh = 0, phase_kw = 0;
 };
 
 Geometry geometry(int B, int C, int H, int W, int pad = PB_KRAD) {
@@ -453,6 +462,20 @@ int run_polynomial(pb_ctx *ctx, const Geometry &g, const void *xsrc, int x_dtype
     return rc;
 }
 
+// The same polynomial with the pure-phase filter in front (deblurring.py:141-169 with not_symmetric=True): one transform over
+// the padded domain (conv_phase.hip) in the place of the three reblurring passes.
+int run_phase_polynomial(pb_ctx *ctx, const Geometry &g, const void *xsrc, int x_dtype, const float *xpadded, float alpha,
+                         float beta, void *dst, int dst_dtype, int clamp01) {
+    PhaseCall c;
+    if (xpadded) { c.src = xpadded; c.src_dtype = PB_F32; c.src_virtual = 0; c.src_pitch = g.pp; c.src_plane = g.pplane; }
+    else { c.src = xsrc; c.src_dtype = x_dtype; c.src_virtual = 1; c.src_pitch = g.W; c.src_plane = g.HW; }
+    c.dst = dst; c.dst_dtype = dst_dtype; c.clamp01 = clamp01;
+    c.B = g.B; c.C = g.C; c.H = g.H; c.W = g.W; c.pad = g.pad;
+    c.taps = g.phase_taps; c.kh = g.phase_kh; c.kw = g.phase_kw;
+    c.alpha = alpha; c.beta = beta;
+    return pb_launch_phase(ctx, c);
+}
+
 struct InverseScratch {
     float *t1, *t2, *y, *ox, *nM;
 };
@@ -465,7 +488,7 @@ int inverse_filter(pb_ctx *ctx, const Geometry &g, const void *src, int src_dtyp
                    int g_dtype = PB_F32) {
     // recomb_cur (only with remove_halo): the halo kernel also adds back the detail layer cur - recomb_smooth
     float *t1 = nullptr, *t2 = nullptr;
-    if (!g.t1h) {
+    if (!g.t1h && !(g.phase_taps && !edgetaping)) {     // (the phase polynomial has scratch of its own; the edgetaper in front of it borrows t1)
         t1 = static_cast<float *>(pb_scratch(ctx, "inv.t1", sizeof(float) * g.P * g.pplane));
         t2 = static_cast<float *>(pb_scratch(ctx, "inv.t2", sizeof(float) * g.P * g.pplane));
         if (!t1 || !t2) return PB_ERR_NOMEM;
@@ -480,11 +503,13 @@ int inverse_filter(pb_ctx *ctx, const Geometry &g, const void *src, int src_dtyp
         xpadded = res;
     }
     if (!remove_halo)
-        return run_polynomial(ctx, g, src, src_dtype, xpadded, info, alpha, beta, boundary, t1, t2, dst, dst_dtype,
-                              final_clamp);
+        return g.phase_taps ? run_phase_polynomial(ctx, g, src, src_dtype, xpadded, alpha, beta, dst, dst_dtype, final_clamp)
+                            : run_polynomial(ctx, g, src, src_dtype, xpadded, info, alpha, beta, boundary, t1, t2, dst, dst_dtype,
+                                             final_clamp);
     float *y = static_cast<float *>(pb_scratch(ctx, "inv.y", sizeof(float) * g.P * g.HW));
     if (!y) return PB_ERR_NOMEM;
-    int rc = run_polynomial(ctx, g, src, src_dtype, xpadded, info, alpha, beta, boundary, t1, t2, y, PB_F32, 0);
+    int rc = g.phase_taps ? run_phase_polynomial(ctx, g, src, src_dtype, xpadded, alpha, beta, y, PB_F32, 0)
+                          : run_polynomial(ctx, g, src, src_dtype, xpadded, info, alpha, beta, boundary, t1, t2, y, PB_F32, 0);
     if (rc) return rc;
     if (!g0x) {
         // grad_img=None (deblurring.py:200-201): the gradients of the image the halo mask blends with -- the crop of the
@@ -1056,6 +1081,7 @@ struct pb_taps {
     int B = 0, kh = 0, kw = 0;
     pb_blur_info *rec_zero = nullptr, *rec_wrap = nullptr;      // records (rec_wrap == rec_zero: point-symmetric as embedded)
     float *tables = nullptr;                                    // tables: B zero-boundary ones, B wrap-boundary ones, B autocorrelations
+    float *raw = nullptr;                                       // the B kh x kw kernels as given (the pure-phase polynomial places them itself: conv_phase.hip)
     BigTaps big_zero, big_wrap;
 };
 
@@ -1122,6 +1148,20 @@ int pb_taps_create(pb_ctx *ctx, int B, int kh, int kw, const float *host_taps, i
     pb_taps *t = new pb_taps();
     t->ctx = ctx; t->B = B; t->kh = kh; t->kw = kw;
     int rc = PB_OK;
+    {
+        void *m = nullptr;
+        const size_t bytes = sizeof(float) * (size_t)B * kh * kw;
+        if (hipMalloc(&m, bytes) != hipSuccess) {
+            delete t;
+            return pb_fail(ctx, PB_ERR_NOMEM, "pb_taps_create: hipMalloc of %d kernels failed", B);
+        }
+        t->raw = static_cast<float *>(m);
+        // (no wait of its own: both forms below end in a stream synchronise before the call returns)
+        if (hipMemcpyAsync(t->raw, host_taps, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+            (void)pb_taps_free(t);
+            return pb_fail(ctx, PB_ERR_HIP, "pb_taps_create: copy of the taps failed");
+        }
+    }
     if (taps_in_records(kh, kw)) {
         bool sym = true;                                     // (as embedded: an even size never is)
         std::vector<float> e(PB_KSIZE * PB_KSIZE);
@@ -1132,7 +1172,7 @@ int pb_taps_create(pb_ctx *ctx, int B, int kh, int kw, const float *host_taps, i
         }
         void *m = nullptr;
         if (hipMalloc(&m, sizeof(pb_blur_info) * (size_t)B * (sym ? 1 : 2)) != hipSuccess) {
-            delete t;
+            (void)pb_taps_free(t);
             return pb_fail(ctx, PB_ERR_NOMEM, "pb_taps_create: hipMalloc of %d records failed", B * (sym ? 1 : 2));
         }
         t->rec_zero = static_cast<pb_blur_info *>(m);
@@ -1143,15 +1183,11 @@ int pb_taps_create(pb_ctx *ctx, int B, int kh, int kw, const float *host_taps, i
         const size_t nt = (size_t)PB_BIG_TABLE * B;
         void *m = nullptr;
         if (hipMalloc(&m, sizeof(float) * (2 * nt + (size_t)PB_BIG_ACORR * B)) != hipSuccess) {
-            delete t;
+            (void)pb_taps_free(t);
             return pb_fail(ctx, PB_ERR_NOMEM, "pb_taps_create: hipMalloc of %d tap tables failed", 2 * B);
         }
         t->tables = static_cast<float *>(m);
-        float *raw = static_cast<float *>(pb_scratch(ctx, "taps.raw", sizeof(float) * (size_t)B * kh * kw));   // (only until the tables are built)
-        rc = raw ? PB_OK : PB_ERR_NOMEM;
-        if (!rc && hipMemcpyAsync(raw, host_taps, sizeof(float) * (size_t)B * kh * kw, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-            rc = pb_fail(ctx, PB_ERR_HIP, "pb_taps_create: copy of the taps failed");
-        if (!rc) rc = pb_build_caller_taps(ctx, raw, B, kh, kw, t->tables, t->tables + nt, t->tables + 2 * nt);
+        rc = pb_build_caller_taps(ctx, t->raw, B, kh, kw, t->tables, t->tables + nt, t->tables + 2 * nt);
         if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = pb_fail(ctx, PB_ERR_HIP, "pb_taps_create: building the tap tables failed");
         t->big_zero.taps = t->tables; t->big_wrap.taps = t->tables + nt;
         t->big_zero.acorr = t->big_wrap.acorr = t->tables + 2 * nt;
@@ -1173,6 +1209,7 @@ int pb_taps_free(pb_taps *t) {
         (void)hipFree(t->rec_zero);
     }
     if (t->tables) (void)hipFree(t->tables);
+    if (t->raw) (void)hipFree(t->raw);
     delete t;
     return PB_OK;
 }
@@ -1244,6 +1281,53 @@ int pb_inverse_filter_taps(pb_ctx *ctx, const void *in, void *out, int dtype, in
         if (rc) return rc;
     }
     return inverse_filter(ctx, g, in, dtype, out, dtype, recs, alpha, beta, boundary, edgetaping, remove_halo, grad0_x, grad0_y, nM, 1);
+}
+
+int pb_inverse_filter_phase_taps(pb_ctx *ctx, const void *in, void *out, int dtype, int B, int C, int H, int W, const pb_taps *taps,
+                                 float alpha, float beta, int edgetaping, int remove_halo, const float *grad0_x,
+                                 const float *grad0_y) {
+    int rc = check_shape(ctx, dtype, B, C, H, W);
+    if (rc) return rc;
+    if (!in || !out || in == out) return pb_fail(ctx, PB_ERR_BADARG, "null or aliased image");
+    if ((grad0_x == nullptr) != (grad0_y == nullptr)) return pb_fail(ctx, PB_ERR_BADARG, "grad0_x and grad0_y: both or neither");
+    Geometry g; const pb_blur_info *recs = nullptr;
+    rc = taps_geometry(ctx, taps, B, C, H, W, PB_WRAP, false, edgetaping != 0, &g, &recs);
+    if (rc) return rc;
+    rc = pb_phase_sides_supported(ctx, g.Hp, g.Wp);
+    if (rc) return rc;
+    PB_HIP(hipSetDevice(ctx->device));
+    g.phase_taps = taps->raw; g.phase_kh = taps->kh; g.phase_kw = taps->kw;
+    float *nM = nullptr;
+    if (remove_halo && grad0_x) {
+        nM = static_cast<float *>(pb_scratch(ctx, "inv.nM", sizeof(float) * g.P));
+        if (!nM) return PB_ERR_NOMEM;
+        rc = pb_grad_energy(ctx, grad0_x, grad0_y, nM, g.P, g.HW);
+        if (rc) return rc;
+    }
+    return inverse_filter(ctx, g, in, dtype, out, dtype, recs, alpha, beta, PB_WRAP, edgetaping, remove_halo, grad0_x, grad0_y, nM, 1);
+}
+
+int pb_compute_polynomial_taps(pb_ctx *ctx, const float *in, float *out, int B, int C, int H, int W, const pb_taps *taps,
+                               float alpha, float beta, int boundary, int not_symmetric) {
+    int rc = check_shape(ctx, PB_F32, B, C, H, W);
+    if (rc) return rc;
+    if (!in || !out || in == out) return pb_fail(ctx, PB_ERR_BADARG, "null or aliased image");
+    Geometry g; const pb_blur_info *recs = nullptr;
+    rc = taps_geometry(ctx, taps, B, C, H, W, boundary, true, false, &g, &recs);
+    if (rc) return rc;
+    if (not_symmetric && boundary != PB_WRAP)
+        return pb_fail(ctx, PB_ERR_BADARG, "not_symmetric with PB_ZERO: the reference's direct form takes the flag and ignores it (deblurring.py:122-138) -- "
+                       "a silent no-op is refused; the pure-phase filter is PB_WRAP's");
+    PB_HIP(hipSetDevice(ctx->device));
+    g.pp = W; g.pplane = g.HW;                              // (the caller's planes are the whole domain, not pitched)
+    if (not_symmetric) {
+        g.phase_taps = taps->raw; g.phase_kh = taps->kh; g.phase_kw = taps->kw;
+        return run_phase_polynomial(ctx, g, in, PB_F32, in, alpha, beta, out, PB_F32, 0);
+    }
+    float *t1 = static_cast<float *>(pb_scratch(ctx, "inv.t1", sizeof(float) * g.P * g.pplane));
+    float *t2 = static_cast<float *>(pb_scratch(ctx, "inv.t2", sizeof(float) * g.P * g.pplane));
+    if (!t1 || !t2) return PB_ERR_NOMEM;
+    return run_polynomial(ctx, g, in, PB_F32, in, recs, alpha, beta, boundary, t1, t2, out, PB_F32, 0);
 }
 
 }  // extern "C"

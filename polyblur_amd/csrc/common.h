@@ -177,6 +177,7 @@ struct pb_ctx {
     // tuning / comparison knobs of single kernels, read once in pb_create (the table of every knob: api.hip, pb_read_knobs)
     int cols_fixed = 1;                  // env PB_COLS_FIXED: 0 = the column transform always by the run-time-plan kernel (grad_cols_kernel), also where lines_fixed.hip holds the plan
     int rows_fixed = 1;                  // env PB_ROWS_FIXED: the same for the row transforms (gray_rows_kernel / grad_rows_kernel)
+    size_t phase_budget = 0;             // pb_set_phase_budget: bytes of complex scratch one group of plane pairs of the pure-phase polynomial may take (conv_phase.hip); 0 = 256 MiB.  One pair is always allowed
     int strip_mode = 0;                  // env PB_STRIP: 1 = rank-1 kernels of full support take the streaming strip body (fp32 planes; --experimental builds only)
 };
 
@@ -317,6 +318,19 @@ int pb_build_big_taps(pb_ctx *ctx, const pb_blur_info *dev_info, int B, int ksiz
 int pb_build_caller_taps(pb_ctx *ctx, const float *dev_raw, int B, int kh, int kw, float *zero, float *wrap, float *acorr);
 int pb_launch_conv_big(pb_ctx *ctx, const ConvPass &p, const BigTaps &big);
 bool pb_conv_fft_feasible(const ConvPass &p);                                // window counts within the kernel's index arithmetic
+// the polynomial with the pure-phase filter (conv_phase.hip; deblurring.py:141-169 with not_symmetric=True): one transform over
+// the whole (H + 2 pad) x (W + 2 pad) domain.  src: (B,C) planes of src_dtype -- un-padded H x W ones addressed in padded
+// coordinates (src_virtual: replicate pad by index clamp) or materialised padded ones --; dst: the (B,C,H,W) interior of dst_dtype;
+// taps: B raw kh x kw kernels in device memory, placed as p2o places them
+struct PhaseCall {
+    const void *src; int src_dtype; int src_virtual; int src_pitch; long src_plane;
+    void *dst; int dst_dtype; int clamp01;
+    int B, C, H, W, pad;
+    const float *taps; int kh, kw;
+    float alpha, beta;
+};
+int pb_launch_phase(pb_ctx *ctx, const PhaseCall &c);
+int pb_phase_sides_supported(pb_ctx *ctx, int Hp, int Wp);                   // PB_ERR_UNSUPPORTED (message set) unless both sides' lines fit LDS
 
 // ------------------------------------------------------------------------------------
 // estimation (estimate.hip)

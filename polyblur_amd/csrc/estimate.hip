@@ -268,19 +268,7 @@ const float *pb_get_interp_weights(pb_ctx *ctx, int n_angles, int n_interp) {
 
 namespace {
 
-pbfft::DevPlan dev_plan(const FftPlan *pl) {
-    pbfft::DevPlan d;
-    d.line_n = pl->n;
-    d.n = pl->bluestein_m ? pl->bluestein_m : pl->n;
-    d.nstage = pl->nstage;
-    for (int i = 0; i < 24; ++i) d.radix[i] = i < pl->nstage ? pl->radix[i] : 1;
-    d.tw = pl->tw;
-    d.drev = pl->drev;
-    d.chirp = pl->chirp;
-    d.bfilt_rev = pl->bfilt_rev;
-    d.dnat = pl->dnat;
-    return d;
-}
+using pbfft::dev_plan;
 
 // ------------------------------------------------------------------------------------
 // gray + min/max

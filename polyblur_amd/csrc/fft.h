@@ -339,6 +339,21 @@ struct DevPlan {
     const float *dnat;        // derivative multiplier / line_n in natural order
 };
 
+// (host) the plan as the kernels take it
+inline DevPlan dev_plan(const FftPlan *pl) {
+    DevPlan d;
+    d.line_n = pl->n;
+    d.n = pl->bluestein_m ? pl->bluestein_m : pl->n;
+    d.nstage = pl->nstage;
+    for (int i = 0; i < 24; ++i) d.radix[i] = i < pl->nstage ? pl->radix[i] : 1;
+    d.tw = pl->tw;
+    d.drev = pl->drev;
+    d.chirp = pl->chirp;
+    d.bfilt_rev = pl->bfilt_rev;
+    d.dnat = pl->dnat;
+    return d;
+}
+
 // natural -> digit-reversed forward DFT of length plan.n (all NB lines)
 __device__ __forceinline__ void forward_dif(float2 *s, const DevPlan &p, int lognb) {
     int L = p.n;
@@ -542,6 +557,49 @@ __device__ __forceinline__ void spectral_derivative(float2 *s, const DevPlan &p,
         __syncthreads();
     }
     (void)nb;
+}
+
+// ---- the two halves of spectral_derivative, for callers that bring a multiplier of their own (conv_phase.hip) -------
+// line_forward: s holds NB interleaved complex lines of length plan.line_n in natural order (room for plan.n entries per
+// line); on return s[k], k < line_n, is the forward DFT of the line -- in digit-reversed order for a direct plan, in
+// natural order for a Bluestein plan.  Two lines that went through the same plan agree position by position, so an
+// element-wise multiplier never needs to know which order that is.
+// line_inverse: s holds conj(Z) in the order line_forward leaves; on return s[p] = conj(sum_k Z[k] exp(+2 pi i p k / N)),
+// p < line_n, in natural order: the conjugate of the inverse transform times N.
+// Both must be called by all threads of the workgroup, after a barrier behind the caller's writes; both end with one.
+__device__ __forceinline__ void bluestein_pass(float2 *s, const DevPlan &p, int lognb) {
+    // X[k] = conj(w[k]) * sum_n (x[n] conj(w[n])) w[k-n],  w[n] = exp(i pi n^2/N)
+    const int N = p.line_n, M = p.n;
+    for (int e = threadIdx.x; e < (M << lognb); e += (int)blockDim.x) {
+        const int n = e >> lognb;
+        float2 v = make_float2(0.f, 0.f);
+        if (n < N) {
+            const float2 w = p.chirp[n];
+            v = cmul(s[e], make_float2(w.x, -w.y));
+        }
+        s[e] = v;
+    }
+    __syncthreads();
+    forward_dif(s, p, lognb);
+    for (int e = threadIdx.x; e < (M << lognb); e += (int)blockDim.x) {
+        const float2 v = cmul(s[e], p.bfilt_rev[e >> lognb]);       // (the filter spectrum holds the 1 / M)
+        s[e] = make_float2(v.x, -v.y);
+    }
+    __syncthreads();
+    forward_dit(s, p, lognb);
+    for (int e = threadIdx.x; e < (N << lognb); e += (int)blockDim.x) {
+        const float2 w = p.chirp[e >> lognb];
+        s[e] = cmul(make_float2(s[e].x, -s[e].y), make_float2(w.x, -w.y));
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ void line_forward(float2 *s, const DevPlan &p, int lognb) {
+    if (p.line_n == p.n) forward_dif(s, p, lognb);
+    else bluestein_pass(s, p, lognb);
+}
+__device__ __forceinline__ void line_inverse(float2 *s, const DevPlan &p, int lognb) {
+    if (p.line_n == p.n) forward_dit(s, p, lognb);
+    else bluestein_pass(s, p, lognb);                                // DFT(conj Z) = conj(N ifft Z)
 }
 
 }  // namespace pbfft

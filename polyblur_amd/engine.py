@@ -120,6 +120,11 @@ class Engine:
         m = {"stencil": capi.PB_DENSE_STENCIL, "auto": capi.PB_DENSE_AUTO}[mode]
         self._check(self.lib.pb_set_dense_eval(self.ctx, m, int(min_phases)))
 
+    def set_phase_budget(self, nbytes: int = 0):
+        """Bytes of complex scratch one group of plane pairs of the pure-phase polynomial may take (0: the default, 256 MiB;
+        one pair is always allowed).  Results do not depend on it (pb_set_phase_budget)."""
+        self._check(self.lib.pb_set_phase_budget(self.ctx, C.c_size_t(int(nbytes))))
+
     def body_selection(self, B: int, iteration: int = -1) -> np.ndarray:
         """(B, 6) int32: per image {tile-spectrum body, halo class, strip, one-pass polynomial, halo x, halo y} of iteration
         `iteration` of the most recent polyblur call (-1: of the most recent estimation / reblurring pass; pb_body_selection)."""
@@ -294,6 +299,20 @@ class Engine:
                                                     float(beta), int(boundary), int(bool(edgetaping)), int(bool(remove_halo)),
                                                     g0x_ptr, g0y_ptr))
 
+    def compute_polynomial_taps_ptr(self, in_ptr: int, out_ptr: int, shape, ks: KernelSet, alpha, beta, boundary=capi.PB_WRAP,
+                                    not_symmetric=False):
+        """compute_polynomial on float32 planes that are the whole domain (pb_compute_polynomial_taps); unclamped"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_compute_polynomial_taps(self.ctx, in_ptr, out_ptr, B, Cc, H, W, ks.handle, float(alpha), float(beta),
+                                                        int(boundary), int(bool(not_symmetric))))
+
+    def inverse_filter_phase_taps_ptr(self, in_ptr: int, out_ptr: int, dtype: int, shape, ks: KernelSet, alpha, beta,
+                                      edgetaping=False, remove_halo=False, g0x_ptr=None, g0y_ptr=None):
+        """the non-blind chain with the pure-phase filter in the polynomial (pb_inverse_filter_phase_taps)"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_inverse_filter_phase_taps(self.ctx, in_ptr, out_ptr, dtype, B, Cc, H, W, ks.handle, float(alpha),
+                                                          float(beta), int(bool(edgetaping)), int(bool(remove_halo)), g0x_ptr, g0y_ptr))
+
     def _taps_call(self, x: np.ndarray, call):
         x = np.ascontiguousarray(x)
         din = self.to_device("np.in", x)
@@ -319,6 +338,20 @@ class Engine:
             g0y = self.to_device("np.g0y", np.ascontiguousarray(grad0[1], np.float32)).ptr
         return self._taps_call(x, lambda i, o: self.inverse_filter_taps_ptr(i, o, _DT[x.dtype], x.shape, ks, alpha, beta, boundary,
                                                                             edgetaping, remove_halo, g0x, g0y))
+
+    def compute_polynomial_taps(self, x: np.ndarray, ks: KernelSet, alpha, beta, boundary=capi.PB_WRAP, not_symmetric=False) -> np.ndarray:
+        x = np.ascontiguousarray(x, np.float32)
+        return self._taps_call(x, lambda i, o: self.compute_polynomial_taps_ptr(i, o, x.shape, ks, alpha, beta, boundary, not_symmetric))
+
+    def inverse_filter_phase_taps(self, x: np.ndarray, ks: KernelSet, alpha, beta, edgetaping=False, remove_halo=False,
+                                  grad0=None) -> np.ndarray:
+        x = np.ascontiguousarray(x)
+        g0x = g0y = None
+        if remove_halo and grad0 is not None:
+            g0x = self.to_device("np.g0x", np.ascontiguousarray(grad0[0], np.float32)).ptr
+            g0y = self.to_device("np.g0y", np.ascontiguousarray(grad0[1], np.float32)).ptr
+        return self._taps_call(x, lambda i, o: self.inverse_filter_phase_taps_ptr(i, o, _DT[x.dtype], x.shape, ks, alpha, beta,
+                                                                              edgetaping, remove_halo, g0x, g0y))
 
     def halo_mask(self, x, y, g0x, g0y) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)

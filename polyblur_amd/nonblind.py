@@ -18,7 +18,14 @@ domain (ValueError); sides above 49, tuple kernels / method='direct_separable', 
 do_edgetaper=True under 'fft' -- a kernel taller than wide, for which the reference's circular pad by the half-width is no
 circular convolution over the domain (NotImplementedError).
 
-The arithmetic is the HIP engine's (include/polyblur_hip.h: pb_taps_create and the three *_taps calls); nothing runs on the CPU.
+``compute_polynomial`` and ``inverse_filtering_nonsymmetric`` bring the reference's cure for kernels that are not
+point-symmetric (deblurring.py:141-169, ``not_symmetric=True``): the image spectrum times the pure-phase filter
+conj(K) / (|K| + 1e-8) before the polynomial.  That is one transform over the whole (padded) domain; both of its sides must
+be line lengths the engine holds in LDS (up to 20480 samples when every prime factor is <= 7, up to 8192 otherwise):
+NotImplementedError before any device work otherwise.  Where |K| falls to fp32 roundoff (about 1e-7 -- a wide Gaussian has
+such bins near Nyquist) the phase of that filter is noise, in the reference as much as here: a property of the method.
+
+The arithmetic is the HIP engine's (include/polyblur_hip.h: pb_taps_create and the *_taps calls); nothing runs on the CPU.
 """
 from __future__ import annotations
 
@@ -185,5 +192,59 @@ def inverse_filtering_rank3(img, kernel, alpha=2, b=4, correlate=False, remove_h
     def call(eng, ks, i, o, s, ex):
         eng.inverse_filter_taps_ptr(i, o, dtype, s, ks, alpha, b, bnd, bool(do_edgetaper), bool(remove_halo),
                                     ex[0] if ex else None, ex[1] if ex else None)
+
+    return _run(img, tensor, dt, shape, taps, per_plane, call, extra)
+
+
+def _check_phase_sides(hp, wp):
+    """the pure-phase filter transforms whole lines of the domain in LDS (pb_fft_length_supported == 1; needs no GPU)"""
+    lib = capi.load_library()
+    for n in (hp, wp):
+        if lib.pb_fft_length_supported(int(n)) != 1:
+            raise NotImplementedError("the pure-phase filter transforms the whole %d x %d domain: a side of %d samples is not held "
+                                      "in LDS (up to 20480 with prime factors <= 7, up to 8192 otherwise)" % (hp, wp, n))
+
+
+def compute_polynomial(img, kernel, alpha, b, method='fft', not_symmetric=False):
+    """deblurring.compute_polynomial (deblurring.py:113-169): a3 K^3 x + a2 K^2 x + a1 K x + b x on ``img``, which is the whole
+    domain (float32; treated as convolve2d treats it); unclamped.  ``not_symmetric=True`` ('fft' only): the pure-phase filter
+    conj(K) / (|K| + 1e-8) first -- for a kernel that is not point-symmetric.  Under 'direct' the reference takes the flag and
+    ignores it; here that is a ValueError.  Where |K| falls to fp32 roundoff the filter's phase is noise (see the module)."""
+    tensor, shape, dt = _check_image(img, allow_half=False)
+    taps, per_plane = _check_kernel(kernel, method, shape, pad_domain=False, circular_only=False)
+    if not_symmetric and method != "fft":
+        raise ValueError("not_symmetric=True is the pure-phase filter of method='fft' (the reference's direct form ignores the flag)")
+    if not_symmetric:
+        _check_phase_sides(shape[2], shape[3])
+    bnd = _BOUNDARY[method]
+    return _run(img, tensor, dt, shape, taps, per_plane,
+                lambda eng, ks, i, o, s, ex: eng.compute_polynomial_taps_ptr(i, o, s, ks, alpha, b, bnd, bool(not_symmetric)))
+
+
+def inverse_filtering_nonsymmetric(img, kernel, alpha=2, b=4, correlate=False, remove_halo=False, do_edgetaper=False,
+                                   grad_img=None):
+    """inverse_filtering_rank3's chain (deblurring.py:211-239) with compute_polynomial(method='fft', not_symmetric=True) in the
+    polynomial's place: replicate pad by w // 2 -> [edgetaper, 'fft'] -> phase-corrected polynomial -> crop -> [halo masking]
+    -> clamp.  float32 or float16 images.  Where |K| falls to fp32 roundoff the filter's phase is noise (see the module)."""
+    tensor, shape, dt = _check_image(img, allow_half=True)
+    taps, per_plane = _check_kernel(kernel, "fft", shape, pad_domain=True, circular_only=bool(do_edgetaper),
+                                    correlate=bool(correlate))
+    pad = taps.shape[-1] // 2
+    _check_phase_sides(shape[2] + 2 * pad, shape[3] + 2 * pad)
+    extra = ()
+    if remove_halo:
+        _check_image_size(*shape[-2:])
+        if grad_img is not None:
+            if not isinstance(grad_img, (tuple, list)) or len(grad_img) != 2:
+                raise ValueError("grad_img must be (grad_x, grad_y)")
+            for gpart in grad_img:
+                if tuple(int(v) for v in gpart.shape) != shape:
+                    raise ValueError("grad_img planes must have the image's shape %r" % (shape,))
+            extra = tuple(grad_img)
+    dtype = capi.PB_F16 if dt == np.float16 else capi.PB_F32
+
+    def call(eng, ks, i, o, s, ex):
+        eng.inverse_filter_phase_taps_ptr(i, o, dtype, s, ks, alpha, b, bool(do_edgetaper), bool(remove_halo),
+                                          ex[0] if ex else None, ex[1] if ex else None)
 
     return _run(img, tensor, dt, shape, taps, per_plane, call, extra)
