@@ -89,6 +89,7 @@ static int pitch4(int w) { return (w + 3) & ~3; }
 //   PB_FFT_FIRST / _ROWS=0|r    the column / row transform's first and last stage: the greedy plan's order, or radix r (default: by line length)
 //   PB_COLS_FIXED=0, PB_ROWS_FIXED=0   the line transforms always by the run-time-plan kernels (estimate.hip), also where
 //                               lines_fixed.hip holds the plan (the tests' bit-identity reference)
+//   PB_POLY_TALL=0|2            one-pass images never / wherever admitted on windows 64 wide and 128 tall (default 1: by the cost model)
 //   PB_STRIP=1                  a measured experiment (conv_strip.hip): read in --experimental builds only
 // A knob stays while a test, bench.py or a script under tools/ names it.  Retired, their alternatives measured and dropped in
 // NOTEBOOK.md -- round 6: PB_ROWS_NT, PB_COLS_WIDE, PB_MAIN_STREAM_BODY, PB_SIDE_STREAM, PB_SIDE_MIN_TILES; after it, with their
@@ -104,7 +105,7 @@ static void pb_read_knobs(pb_ctx *ctx) {
 #endif
     geti("PB_EST_GRAY_ROWS", ctx->est_gray_rows); geti("PB_EST_LEAN", ctx->est_lean); geti("PB_DT_ROWS_REG", ctx->dt_rows_reg); geti("PB_DT_COLS_STRIP", ctx->dt_cols_strip); geti("PB_DT_COLS_COOP", ctx->dt_cols_coop);
     geti("PB_FFT_EXT_RADIX", ctx->fft_ext_radix); geti("PB_FFT_FIRST", ctx->fft_first); geti("PB_FFT_FIRST_ROWS", ctx->fft_first_rows); geti("PB_COLS_FIXED", ctx->cols_fixed); geti("PB_ROWS_FIXED", ctx->rows_fixed);
-    geti("PB_POLY1", ctx->poly_mode);
+    geti("PB_POLY1", ctx->poly_mode); geti("PB_POLY_TALL", ctx->poly_tall);
     geti("PB_POLY_ALWAYS", ctx->poly_always); geti("PB_POLY_PADDED", ctx->poly_padded); geti("PB_TAPER_RING", ctx->taper_ring); geti("PB_ZERO_RING", ctx->zero_ring); getl("PB_ZERO_RING_MIN_PAIRS", ctx->zero_ring_min_pairs);
 }
 
@@ -401,7 +402,15 @@ PolySpec poly_spec(pb_ctx *ctx, const ConvPass *steps, float alpha, float beta, 
     const int always = (mode == 3 && gaussians && ctx->poly_always) ? 1 : 0;
     // (under the zero boundary only that class takes one pass: interior by the window pass, frame by three ring steps)
     if (steps[0].boundary != PB_WRAP && !always) return no_poly();
-    return PolySpec{mode, alpha / 2 - beta + 2, 3 * beta - alpha - 6, 5 - 3 * beta + alpha / 2, beta, PB_POLY_GAIN, PB_POLY_MIN_AREA, PB_POLY_COST128, always};
+    // (windows 64 wide and 128 tall, conv_wfft.hip: the composite pass from an un-tapered fp32 image to an fp32 plane under the
+    // wrap boundary, an image at least one such window tall -- facts of the call, PolySpec.tall; that the taps are point-symmetric
+    // -- an odd ker_size grid -- is what every one-pass form asks of a record, khat.h)
+    const ConvPass &f = steps[0], &l = steps[2];
+    const bool tall_ok = mode >= 2 && f.boundary == PB_WRAP && f.in_dtype == PB_F32 && f.x_dtype == PB_F32 && l.out_dtype == PB_F32 &&
+                         f.in_kind == SRC_VIRTUAL && f.epilogue == EPI_HORNER && f.H >= 128;
+    const int tall = tall_ok ? std::min(std::max(ctx->poly_tall, 0), 2) : 0;
+    return PolySpec{mode, alpha / 2 - beta + 2, 3 * beta - alpha - 6, 5 - 3 * beta + alpha / 2, beta, PB_POLY_GAIN, PB_POLY_MIN_AREA, PB_POLY_COST128, always,
+                    tall, PB_POLY_COST_TALL};
 }
 
 // y = a3 K^3 x + a2 K^2 x + a1 K x + beta x by Horner, three stencil passes (deblurring.py:122-138).

@@ -53,11 +53,16 @@ struct ProfRec {
 // options, image size, ker_size) alone that every composite fits a 128 x 128 window and every kernel is a point-symmetric
 // Gaussian the estimation itself builds: the polynomial then issues the two window launches and nothing else (no launch
 // that finds no work, no side stream), without the host ever reading a record back.
-struct PolySpec { int on; float a3, a2, a1, b; float gain; int min_area; float cost128; int always; };
-inline PolySpec no_poly() { return PolySpec{0, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 0.f, 0}; }
+// tall (with on >= 2): the host vouches that the composite pass reads and writes fp32 planes of at least 128 rows under the
+// wrap boundary, un-tapered (that the taps are point-symmetric, an odd ker_size grid, is looked at on the device or vouched for
+// by `always`, as for every one-pass form: khat.h) -- an image may then take its one pass on windows 64 wide and
+// 128 tall (conv_wfft.hip: wave_tall, pb_fft_sel.pad_[0] = 1): 1 = where the cost model prices that form lowest (cost_tall = a
+// tall window in 64 x 64 window pairs), 2 = every image it admits (env PB_POLY_TALL).
+struct PolySpec { int on; float a3, a2, a1, b; float gain; int min_area; float cost128; int always; int tall; float cost_tall; };
+inline PolySpec no_poly() { return PolySpec{0, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 0.f, 0, 0, 0.f}; }
 inline bool same_spec(const PolySpec &x, const PolySpec &y) {
     return x.on == y.on && x.always == y.always &&
-           (!x.on || (x.a3 == y.a3 && x.a2 == y.a2 && x.a1 == y.a1 && x.b == y.b && (x.cost128 > 0.f) == (y.cost128 > 0.f)));
+           (!x.on || (x.a3 == y.a3 && x.a2 == y.a2 && x.a1 == y.a1 && x.b == y.b && (x.cost128 > 0.f) == (y.cost128 > 0.f) && x.tall == y.tall));
 }
 
 // rf = window halo class of the workgroup form (conv_fft.hip): 4, 8 or 12 -- 0 when only the wave form can run the image
@@ -178,6 +183,7 @@ struct pb_ctx {
     int cols_fixed = 1;                  // env PB_COLS_FIXED: 0 = the column transform always by the run-time-plan kernel (grad_cols_kernel), also where lines_fixed.hip holds the plan
     int rows_fixed = 1;                  // env PB_ROWS_FIXED: the same for the row transforms (gray_rows_kernel / grad_rows_kernel)
     size_t phase_budget = 0;             // pb_set_phase_budget: bytes of complex scratch one group of plane pairs of the pure-phase polynomial may take (conv_phase.hip); 0 = 256 MiB.  One pair is always allowed
+    int poly_tall = 1;                   // env PB_POLY_TALL: one-pass images on windows 64 wide and 128 tall -- 0 = never, 1 = where the cost model of khat.h prices them lowest, 2 = every image the form admits
     int strip_mode = 0;                  // env PB_STRIP: 1 = rank-1 kernels of full support take the streaming strip body (fp32 planes; --experimental builds only)
 };
 
@@ -242,6 +248,17 @@ constexpr int PB_POLY_MIN_TX = 24, PB_POLY_MIN_TY = 16;     // smallest tile of 
 // cost model of the one-pass forms (khat.h; the sweeps: NOTEBOOK.md), what PolySpec.gain / min_area / cost128 are filled from
 constexpr float PB_POLY_GAIN = 0.7f;                       // a Horner step costs more than a one-pass window of the same tile (x operand, two launches more)
 constexpr int PB_POLY_MIN_AREA = 768;                      // one pass over 768-sample tiles takes what three rank-1 stencil passes take
+constexpr int PB_TALL_MIN_AREA = 2 * PB_POLY_MIN_AREA;         // ... and its smallest tile: what the smallest pair of 64 x 64 tiles keeps (the job grid grows no longer than theirs)
+constexpr int PB_TALL_MAX_HY = 36;                         // largest row halo of a 64 x 128 window (every composite there is; tiles of at least 56 rows), columns as PB_POLY_MIN_TX
+// a window 64 wide and 128 tall in pairs of 64 x 64 ones: measured 1.22 on the headline's second estimate (sigma 1.66 / rho 1.01 at
+// 66 degrees, halos 12 / 16; one 4K polynomial, tools/tall_timing.py: 84.4 us for 6624 tall jobs = 12.74 ns a job against 102.1 us
+// for 9792 pair jobs = 10.42 ns; a second visit: 77.1 against 95.0 us, 1.20; 1.11 on the third estimate)
+constexpr float PB_POLY_COST_TALL = 1.22f;
+// what a 128 x 128 window pair costs WITHOUT the launch PB_POLY_COST128 charges it with (measured 6 - 6.5): what the tall form is
+// compared with -- it takes no launch off an image's polynomial, the 128 x 128 launch is issued either way.  Measured on the
+// headline's first estimate (halos 16 / 20, tools/tall_timing.py): 1500 pairs of 128 x 128 windows 95.8 us, 9000 tall windows 103.7 us
+// -- the model keeps the 128 x 128 form there at 6.5 (7.4e-4 against the tall form's 8.7e-4) and would leave it at 8 (9.5e-4)
+constexpr float PB_POLY_COST128_BARE = 6.5f;
 constexpr float PB_POLY_COST128 = 8.0f;                    // a 128 x 128 window pair in pairs of 64 x 64 (measured 6 - 6.5 at 4K, plus a launch of its own in the pipeline)
 
 

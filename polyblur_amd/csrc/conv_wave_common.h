@@ -126,6 +126,109 @@ __device__ __forceinline__ void fft64_inv_stage2(cf (&v)[64]) {
 #undef PB_S
 }
 
+// ---------------------------------------------------------------------------------------------
+// A REAL line of 128 samples in the same 64 registers: register n holds samples 2 n (real part) and 2 n + 1 (imaginary part),
+// z = even + i odd.  Behind fft64 the standard real-input split turns Z into the line's own transform X[k], k = 0 .. 64:
+// X[k] = E[k] + W128^k O[k] with E = (Z[k] + conj Z[64 - k]) / 2, O = -i (Z[k] - conj Z[64 - k]) / 2; X[k] stays where Z[k]
+// was (register 8 (k & 7) + (k >> 3)), k = 1 .. 63, and the two real bins share register 0 as X[0] + i X[64].  The merge is its
+// inverse in front of the inverse transform.  Both leave out the halving: the spectrum carries the factor 4 (khat.h).
+// Every multiply-add is an explicit FMA, as in fft.h; register numbers and twiddles are compile-time constants.
+// ---------------------------------------------------------------------------------------------
+// cos / sin (2 pi k / 128), k = 0 .. 32
+static __device__ const float kCr128[33] = {
+    1.0f, 0.9987954497337341f, 0.9951847195625305f, 0.9891765117645264f, 0.9807852506637573f, 0.9700312614440918f,
+    0.9569403529167175f, 0.9415440559387207f, 0.9238795042037964f, 0.903989315032959f, 0.8819212913513184f,
+    0.8577286005020142f, 0.8314695954322815f, 0.803207516670227f, 0.7730104327201843f, 0.7409511208534241f,
+    0.7071067690849304f, 0.6715589761734009f, 0.6343932747840881f, 0.5956993103027344f, 0.5555702447891235f,
+    0.5141027569770813f, 0.4713967442512512f, 0.4275550842285156f, 0.3826834261417389f, 0.3368898630142212f,
+    0.290284663438797f, 0.24298018217086792f, 0.19509032368659973f, 0.1467304676771164f, 0.0980171412229538f,
+    0.049067676067352295f, 0.0f};
+static __device__ const float kSr128[33] = {
+    0.0f, 0.049067676067352295f, 0.0980171412229538f, 0.1467304676771164f, 0.19509032368659973f, 0.24298018217086792f,
+    0.290284663438797f, 0.3368898630142212f, 0.3826834261417389f, 0.4275550842285156f, 0.4713967442512512f,
+    0.5141027569770813f, 0.5555702447891235f, 0.5956993103027344f, 0.6343932747840881f, 0.6715589761734009f,
+    0.7071067690849304f, 0.7409511208534241f, 0.7730104327201843f, 0.803207516670227f, 0.8314695954322815f,
+    0.8577286005020142f, 0.8819212913513184f, 0.903989315032959f, 0.9238795042037964f, 0.9415440559387207f,
+    0.9569403529167175f, 0.9700312614440918f, 0.9807852506637573f, 0.9891765117645264f, 0.9951847195625305f,
+    0.9987954497337341f, 1.0f};
+constexpr int reg_of_freq(int k) { return 8 * (k & 7) + (k >> 3); }
+template <int K> __device__ __forceinline__ void real_split_pair(cf (&v)[64]) {
+    constexpr int ra = reg_of_freq(K), rb = reg_of_freq(64 - K);
+    const float c = kCr128[K], s = kSr128[K];
+    const cf A = v[ra], B = v[rb];
+    const float ex = A.x + B.x, ey = A.y - B.y, dx = A.x - B.x, dy = A.y + B.y;
+    v[ra] = (cf){fmaf(c, dy, fmaf(-s, dx, ex)), fmaf(-c, dx, fmaf(-s, dy, ey))};
+    v[rb] = (cf){fmaf(-c, dy, fmaf(s, dx, ex)), fmaf(-c, dx, fmaf(-s, dy, -ey))};
+}
+template <int K> __device__ __forceinline__ void real_merge_pair(cf (&v)[64]) {
+    constexpr int ra = reg_of_freq(K), rb = reg_of_freq(64 - K);
+    const float c = kCr128[K], s = kSr128[K];
+    const cf P = v[ra], B = v[rb];
+    const float ex = P.x + B.x, ey = P.y - B.y, dx = P.x - B.x, dy = P.y + B.y;
+    v[ra] = (cf){fmaf(-c, dy, fmaf(-s, dx, ex)), fmaf(c, dx, fmaf(-s, dy, ey))};
+    v[rb] = (cf){fmaf(c, dy, fmaf(s, dx, ex)), fmaf(c, dx, fmaf(-s, dy, -ey))};
+}
+#define PB_EACH31(F) F(1) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11) F(12) F(13) F(14) F(15) F(16) F(17) F(18) F(19) F(20) \
+    F(21) F(22) F(23) F(24) F(25) F(26) F(27) F(28) F(29) F(30) F(31)
+__device__ __forceinline__ void real_split(cf (&v)[64]) {
+#define PB_S(i) real_split_pair<i>(v);
+    PB_EACH31(PB_S)
+#undef PB_S
+    v[reg_of_freq(32)] = (cf){2.f * v[reg_of_freq(32)].x, -2.f * v[reg_of_freq(32)].y};
+    v[0] = (cf){2.f * (v[0].x + v[0].y), 2.f * (v[0].x - v[0].y)};
+}
+__device__ __forceinline__ void real_merge(cf (&v)[64]) {
+#define PB_S(i) real_merge_pair<i>(v);
+    PB_EACH31(PB_S)
+#undef PB_S
+    v[reg_of_freq(32)] = (cf){2.f * v[reg_of_freq(32)].x, -2.f * v[reg_of_freq(32)].y};
+    v[0] = (cf){v[0].x + v[0].y, v[0].x - v[0].y};
+}
+// The centre stages of a transformed row of such a window (lane = row frequency): as centre_stage, and on lane 0 -- whose row
+// carries the two real bins 0 and 64, with different spectra -- the term Hd[kx] conj(Z[(64 - kx) mod 64]) beside Hs[kx] Z[kx]
+// (Hs in lane 0's column of the spectrum; Hd: 64 wave-uniform values; f = 1 on lane 0, 0 elsewhere: the other lanes add an
+// exact zero).  Frequency K1 + 8 k2 of group K1 meets (8 - K1) + 8 (7 - k2) of group 8 - K1: the groups go in pairs, 0 and 4
+// with themselves.
+template <int K1> __device__ __forceinline__ void centre_finish(cf (&v)[64], cf (&b)[8]) {
+    ibf8(b);
+#pragma unroll
+    for (int n2 = 0; n2 < 8; ++n2) {
+        const int m = (n2 * K1) & 63;
+        v[8 * K1 + n2] = m ? cmul_conj_s(b[n2], (cf){kC64[m], -kS64[m]}) : b[n2];
+    }
+}
+template <int K1> __device__ __forceinline__ void centre_self_real(cf (&v)[64], const float (&kh)[8], const PB_CONSTANT float *hd, float f) {
+    static_assert(K1 == 0 || K1 == 4, "groups 0 and 4 meet themselves");
+    cf b[8], o[8];
+#pragma unroll
+    for (int n2 = 0; n2 < 8; ++n2) b[n2] = v[8 * K1 + n2];
+    bf8(b);
+#pragma unroll
+    for (int k2 = 0; k2 < 8; ++k2) {
+        const int p = K1 == 0 ? ((8 - k2) & 7) : 7 - k2;
+        const float g = f * hd[8 * K1 + k2];
+        o[k2] = (cf){fmaf(g, b[p].x, b[k2].x * kh[k2]), fmaf(-g, b[p].y, b[k2].y * kh[k2])};
+    }
+    centre_finish<K1>(v, o);
+}
+template <int KA, int KB> __device__ __forceinline__ void centre_pair_real(cf (&v)[64], const float (&kha)[8], const float (&khb)[8],
+                                                                           const PB_CONSTANT float *hd, float f) {
+    static_assert(KA + KB == 8 && KA != KB, "groups K1 and 8 - K1");
+    cf b[8], c[8], ob[8], oc[8];
+#pragma unroll
+    for (int n2 = 0; n2 < 8; ++n2) { b[n2] = v[8 * KA + n2]; c[n2] = v[8 * KB + n2]; }
+    bf8(b);
+    bf8(c);
+#pragma unroll
+    for (int k2 = 0; k2 < 8; ++k2) {
+        const float ga = f * hd[8 * KA + k2], gb = f * hd[8 * KB + k2];
+        ob[k2] = (cf){fmaf(ga, c[7 - k2].x, b[k2].x * kha[k2]), fmaf(-ga, c[7 - k2].y, b[k2].y * kha[k2])};
+        oc[k2] = (cf){fmaf(gb, b[7 - k2].x, c[k2].x * khb[k2]), fmaf(-gb, b[7 - k2].y, c[k2].y * khb[k2])};
+    }
+    centre_finish<KA>(v, ob);
+    centre_finish<KB>(v, oc);
+}
+
 // v_permlane32_swap: lanes 32..63 of `hi_part` <-> lanes 0..31 of `lo_part`
 __device__ __forceinline__ void swap_halves(cf &hi_part, cf &lo_part) {
     typedef unsigned u2 __attribute__((ext_vector_type(2)));

@@ -50,11 +50,12 @@ struct WGeom { int ow, oh; };
 struct WJobs { int pairs_x, njobs, per; float inv_pairs_x; };      // of one image: window pairs per row, per plane, per plane and XCD
 // n / d for 0 <= n < 2^21 with the hardware's reciprocal (1 ulp): exact -- (n + 1/2) / d is at least 1 / (2 d) away from an integer
 __device__ __forceinline__ int div_rcp(int n, float rcp_d) { return (int)(((float)n + 0.5f) * rcp_d); }
-__device__ __forceinline__ WJobs jobs_of(const WGeom &g, int hx, int hy) {
-    const int Tx = FT_N - 2 * hx, Ty = FT_N - 2 * hy;
+// tall: the image's jobs are single windows 64 wide and 128 tall (wave_tall), not pairs of 64 x 64 ones
+__device__ __forceinline__ WJobs jobs_of(const WGeom &g, int hx, int hy, bool tall) {
+    const int Tx = FT_N - 2 * hx, Ty = (tall ? 2 * FT_N : FT_N) - 2 * hy;
     const int tiles_x = div_rcp(g.ow + Tx - 1, __builtin_amdgcn_rcpf((float)Tx)), tiles_y = div_rcp(g.oh + Ty - 1, __builtin_amdgcn_rcpf((float)Ty));
     WJobs j;
-    j.pairs_x = (tiles_x + 1) >> 1;
+    j.pairs_x = tall ? tiles_x : (tiles_x + 1) >> 1;
     j.njobs = j.pairs_x * tiles_y;
     j.per = (j.njobs + 7) >> 3;
     j.inv_pairs_x = __builtin_amdgcn_rcpf((float)j.pairs_x);
@@ -605,6 +606,212 @@ __device__ __forceinline__ void wave_pair(const ConvPass &a, const pb_blur_info 
     PB_TRT(13);
 }
 
+// One window 64 columns wide and 128 rows TALL of a one-pass polynomial (pb_fft_sel.pad_[0]; PolySpec.tall: fp32 planes at both
+// ends, wrap boundary, no x operand, no taper, no ring).  The 64 complex registers of a lane hold its column's 128 REAL samples:
+// register n = rows (2 n + hy) mod 128 (real part) and (2 n + 1 + hy) mod 128 (imaginary part) -- hy is even: a register's two
+// rows never straddle the rotation, and the tile's Ty = 128 - 2 hy rows come out in registers 0 .. Ty / 2 - 1.  The column
+// transform is fft64 followed by the real-input split (conv_wave_common.h): bins 1 .. 63 complex, bins 0 and 64 -- both real --
+// together in register 0; transposes and row transforms as in wave_pair; lane 0 of the row phase carries those two real rows,
+// whose spectra differ: centre_self_real / centre_pair_real.  The row halo is paid once for what a pair of 64 x 64 windows
+// pays twice: a job keeps Tx (128 - 2 hy) samples of 8192 instead of 2 Tx (64 - 2 hy).
+//   Load: LDS-DMA in 16-byte pieces, one wave instruction = four window rows of 256 bytes = two registers, through the same two
+// 8 KB buffers and with the same waits as wave_pair's; windows that leave the source or are off the 16-byte grid gather four
+// bytes per lane through the boundary model, rows mapped on the scalar side, columns per lane.
+//   Store: the tile goes through the LDS tile (64 rows of 64 floats per half) and leaves in 16-byte row pieces; a tile off the
+// 16-byte grid or cut by the region's right end is stored sample by sample from the registers.
+__device__ __forceinline__ void wave_tall(const ConvPass &a, int plane, int ty, int txi, int hx, int hy, char *zb, const float *kp) {
+    constexpr int TN = 2 * FT_N;
+    const int Tx = FT_N - 2 * hx, Ty = TN - 2 * hy;
+    float2 *Z = reinterpret_cast<float2 *>(zb);
+    float *Zf = reinterpret_cast<float *>(zb);
+    const OutRegion rg = out_region(a);
+    const int oy0 = rg.y_lo + ty * Ty, ox0 = rg.x_lo + txi * Tx;    // the tile's first row / column, padded coordinates
+    const int wx = ox0 - hx, wy0 = oy0 - hy;                        // the window's
+    const int wrap_r = TN - hy;                                     // rotated rows wrap_r .. 127 are the hy rows above the tile
+    const int lane = threadIdx.x & 63;
+    const float *ipl = static_cast<const float *>(a.in) + (long)plane * a.in_plane;
+    float *opl = static_cast<float *>(a.out) + (long)plane * a.out_plane;
+    const int Hp = a.H + 2 * a.pad, Wp = a.W + 2 * a.pad;
+    cf v[64];
+    {
+        const brsrc rin = plane_rsrc(ipl, a.in_plane);
+        const int lo = a.in_kind == SRC_VIRTUAL ? a.pad : 0;
+        const int pitchb = a.in_pitch * 4;
+        lds_char *zl = lds_ptr(zb);
+        // chunk k = the registers 8 j + 2 k, 8 j + 2 k + 1 (j = 0 .. 7), as in wave_pair: an LDS row of 128 floats is one register --
+        // floats 0 .. 63 its even row, 64 .. 127 its odd row -- and every lane picks its column's two samples of either register
+        // with one ds_read2_b32
+        const unsigned la = lds_addr(zb) + (unsigned)lane * 4u;
+        auto pick = [&](int k, int buf) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const unsigned ad = la + (unsigned)(buf * 8192 + j * 1024);
+                asm volatile("ds_read2_b32 %0, %1 offset1:64" : "=v"(v[8 * j + 2 * k]) : "v"(ad));
+                asm volatile("ds_read2_b32 %0, %1 offset0:128 offset1:192" : "=v"(v[8 * j + 2 * k + 1]) : "v"(ad));
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[2 * k]), "+v"(v[2 * k + 1]), "+v"(v[8 + 2 * k]), "+v"(v[9 + 2 * k]), "+v"(v[16 + 2 * k]),
+                         "+v"(v[17 + 2 * k]), "+v"(v[24 + 2 * k]), "+v"(v[25 + 2 * k]), "+v"(v[32 + 2 * k]), "+v"(v[33 + 2 * k]), "+v"(v[40 + 2 * k]),
+                         "+v"(v[41 + 2 * k]), "+v"(v[48 + 2 * k]), "+v"(v[49 + 2 * k]), "+v"(v[56 + 2 * k]), "+v"(v[57 + 2 * k]) :: "memory");
+        };
+        if (wy0 >= lo && wy0 + TN <= Hp - lo && wx >= lo && wx + FT_N <= Wp - lo && ((a.in_pitch | (wx - lo)) & 3) == 0) {
+            // byte offset of rotated row r in the source plane
+            auto rowoff = [&](int r) -> int { return (oy0 - lo + r - (r >= wrap_r ? TN : 0)) * pitchb; };
+            // lane -> (row of the instruction's four, piece of its sixteen).  The one instruction whose four rows straddle the
+            // rotation (hy = 2 mod 4: rotated rows wrap_r - 2 .. wrap_r + 1 = window rows 126, 127, 0, 1) is addressed from
+            // the window's first row with a lane offset of its own.
+            const unsigned colb = (unsigned)((wx - lo + 4 * (lane & 15)) * 4);
+            const unsigned vo = (unsigned)((lane >> 4) * pitchb) + colb;
+            const unsigned vos = (unsigned)((lane < 32 ? TN - 2 + (lane >> 4) : (lane >> 4) - 2) * pitchb) + colb;
+            auto request = [&](int k, int buf) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int r0 = 16 * j + 4 * k;
+                    const bool straddle = r0 + 2 == wrap_r;
+                    dma16<0>(rin, zl + buf * 8192 + j * 1024, straddle ? vos : vo, rowoff(straddle ? r0 + 2 : r0));
+                }
+            };
+            request(0, 0); request(1, 1);
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            pick(0, 0);
+            request(2, 0);
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            pick(1, 1);
+            request(3, 1);
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            pick(2, 0);
+            wait_vm0();
+            pick(3, 1);
+        } else {
+            // (planes are at least a window tall -- PolySpec.tall --: one conditional step brings a row into the circular domain)
+            const unsigned gcol = (unsigned)map_axis(wx + lane, a.W, a.in_kind, PB_WRAP, a.pad) * 4u;
+            const int base = __builtin_amdgcn_readfirstlane(wrap_idx(oy0, Hp));
+            const bool virt_in = a.in_kind == SRC_VIRTUAL;
+            auto gather = [&](int k, int buf) {
+#pragma unroll
+                for (int i = 0; i < 32; ++i) {         // LDS row of 64 floats i of the chunk = rotated row 16 (i >> 2) + 4 k + (i & 3)
+                    const int r = 16 * (i >> 2) + 4 * k + (i & 3);
+                    int pr = base + r - (r >= wrap_r ? TN : 0);
+                    pr += pr < 0 ? Hp : 0;
+                    pr -= pr >= Hp ? Hp : 0;
+                    const int so = (virt_in ? min(max(pr - a.pad, 0), a.H - 1) : pr) * pitchb;
+                    dma4<0>(rin, zl + buf * 8192 + i * 256, gcol, so);
+                }
+            };
+            gather(0, 0); gather(1, 1);
+            asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
+            pick(0, 0);
+            gather(2, 0);
+            asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
+            pick(1, 1);
+            gather(3, 1);
+            asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
+            pick(2, 0);
+            wait_vm0();
+            pick(3, 1);
+        }
+    }
+    fft64_fwd(v);                                               // columns: the packed line, then its own transform
+    real_split(v);
+    transpose64(v, Z, lane);
+    {
+        // the spectrum on the 64 x 128 grid, [x position][lane] (khat.h), in the ring of wave_pair -- the groups in the order the
+        // paired centre stages take them -- and behind it the 64 wave-uniform values of lane 0's second term
+        const brsrc rk = plane_rsrc(kp, (long)FT_N * FT_N);
+        const PB_CONSTANT float *hd = as_constant(kp + FT_N * FT_N);
+        const float f0 = lane == 0 ? 1.f : 0.f;
+        float kh[4][8];
+        auto khload = [&](int slot, int grp) {
+#pragma unroll
+            for (int k2 = 0; k2 < 8; ++k2) kh[slot][k2] = BufIO<float>::ld(rk, (unsigned)lane * 4u, (8 * grp + k2) * (FT_N * 4));
+        };
+        khload(0, 0); khload(1, 1); khload(2, 7); khload(3, 2);
+        __builtin_amdgcn_sched_barrier(0);
+        fft64_fwd_stage1(v);                                    // rows
+        centre_self_real<0>(v, kh[0], hd, f0); khload(0, 6); __builtin_amdgcn_sched_barrier(0);
+        centre_pair_real<1, 7>(v, kh[1], kh[2], hd, f0); khload(1, 3); khload(2, 5); __builtin_amdgcn_sched_barrier(0);
+        centre_pair_real<2, 6>(v, kh[3], kh[0], hd, f0); khload(3, 4); __builtin_amdgcn_sched_barrier(0);
+        centre_pair_real<3, 5>(v, kh[1], kh[2], hd, f0);
+        centre_self_real<4>(v, kh[3], hd, f0);
+    }
+    fft64_inv_stage1(v);
+    transpose64(v, Z, lane);
+    real_merge(v);                                              // columns
+    fft64_inv_stage2(v);
+    fft64_inv_stage1(v);
+
+    // ---- epilogue: lane = window column again, register n = tile rows 2 n and 2 n + 1 ----
+    const int oo = a.out_kind == OUT_INTERIOR ? a.pad : 0;
+    const int opitchb = a.out_pitch * 4;
+    const brsrc ro = plane_rsrc(opl, a.out_plane);
+    const bool colin = lane >= hx && lane < FT_N - hx;
+    const float sc = a.scale;
+    const float clo = a.clamp01 ? 0.f : -INFINITY, chi = a.clamp01 ? 1.f : INFINITY;
+    const int tyr = min(Ty, rg.y_hi - oy0);                     // rows of the tile inside the output region
+    if (((a.out_pitch | (ox0 - oo)) & 3) == 0 && ox0 + Tx <= rg.x_hi) {
+        // C pieces per row, rounds of sixteen rows: lane -> (row of the round, piece) for each of a round's four stores
+        const int C = Tx >> 2;
+        const float invC = __builtin_amdgcn_rcpf((float)C);
+        int rlk[4], chk[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int e = 64 * k + lane;
+            rlk[k] = div_small(e, invC); chk[k] = e - rlk[k] * C;                 // (e < 256, C = 6 .. 14: exact)
+        }
+        const int oso = (oy0 - oo) * opitchb + (ox0 - oo) * 4;
+        auto round = [&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+            const int left = tyr - 16 * q;
+            f4v acc[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] = *reinterpret_cast<const f4v *>(Zf + (16 * (q & 3) + min(rlk[k], 15)) * FT_N + 4 * chk[k]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                f4v o;
+                o.x = __builtin_amdgcn_fmed3f(sc * acc[k].x, clo, chi); o.y = __builtin_amdgcn_fmed3f(sc * acc[k].y, clo, chi);
+                o.z = __builtin_amdgcn_fmed3f(sc * acc[k].z, clo, chi); o.w = __builtin_amdgcn_fmed3f(sc * acc[k].w, clo, chi);
+                const bool ok = rlk[k] < min(left, 16);
+                st_b128(ro, ok ? (unsigned)(rlk[k] * opitchb + chk[k] * 16) : kNoAccess, oso + 16 * q * opitchb, o);
+            }
+        };
+        float *zt = Zf + (lane - hx);
+        auto put_half = [&](auto hc) {
+            constexpr int h = decltype(hc)::value;
+            if (colin) {
+#pragma unroll
+                for (int i = 0; i < 32; ++i) { zt[2 * i * FT_N] = v[32 * h + i].x; zt[(2 * i + 1) * FT_N] = v[32 * h + i].y; }
+            }
+        };
+        typedef std::integral_constant<int, 0> Q0; typedef std::integral_constant<int, 1> Q1; typedef std::integral_constant<int, 2> Q2;
+        typedef std::integral_constant<int, 3> Q3; typedef std::integral_constant<int, 4> Q4; typedef std::integral_constant<int, 5> Q5;
+        typedef std::integral_constant<int, 6> Q6; typedef std::integral_constant<int, 7> Q7;
+        put_half(Q0{});
+        wave_lds_fence();
+        round(Q0{}); round(Q1{}); round(Q2{}); round(Q3{});
+        wave_lds_fence();
+        put_half(Q1{});                                         // (behind the first half's reads: a wave's LDS operations execute in order)
+        wave_lds_fence();
+        if (tyr > 64) {
+            round(Q4{});
+            if (tyr > 80) {
+                round(Q5{});
+                if (tyr > 96) {
+                    round(Q6{});
+                    if (tyr > 112) round(Q7{});
+                }
+            }
+        }
+        return;
+    }
+    const bool okc = colin && wx + lane < rg.x_hi;
+    const unsigned ooff = okc ? (unsigned)(wx + lane - oo) * 4u : kNoAccess;
+#pragma unroll
+    for (int n = 0; n < 64; ++n) {
+        const int so = (oy0 + 2 * n - oo) * opitchb;
+        BufIO<float>::st(ro, 2 * n < tyr ? ooff : kNoAccess, so, __builtin_amdgcn_fmed3f(sc * v[n].x, clo, chi));
+        BufIO<float>::st(ro, 2 * n + 1 < tyr ? ooff : kNoAccess, so + opitchb, __builtin_amdgcn_fmed3f(sc * v[n].y, clo, chi));
+    }
+}
+
 // Whether a pair takes the all-16-byte path: an fp32 or fp16 window, plain Horner epilogue, both windows inside the source
 // without boundary mapping, both tiles complete inside the output region, the x operand addressed without clamping, and
 // rows / origins on 16-byte boundaries.
@@ -732,20 +939,24 @@ __global__ __launch_bounds__(64, 2) void conv_wfft_kernel(const ConvPass a, cons
     const int q = (int)(blockIdx.x & 7u);
     int rem = (int)(blockIdx.x >> 3);                  // position in the list
     int img = 0, hx = 0, hy = 0;
-    bool fold = false;
+    bool fold = false, tall = false;
+    // (windows 64 wide and 128 tall: a one-pass record says so, and only the instantiation of the planes PolySpec.tall vouches for
+    // carries the body)
+    constexpr bool kTall = std::is_same<TIn, float>::value && std::is_same<TX, float>::value && std::is_same<TOut, float>::value && !ZERO;
     if (B == 1) {
         // (one image: its record is read on the scalar side -- no trip through the vector memory queue)
         const PB_CONSTANT pb_fft_sel *s0 = as_constant(a.fsel);
         if (!s0->use_fft || s0->poly == 2 || !poly_match(a.poly, s0->poly)) return;     // (poly == 2: conv_w128.hip's image)
         hx = s0->hx; hy = s0->hy;
         fold = a.poly == 2 && s0->poly != 0;
+        tall = kTall && s0->poly == 1 && s0->pad_[0] != 0;
     } else {
         // list entries of image i: its share of every plane
         auto share_of = [&](int i) -> int {
             if (i >= B) return 0;
             const pb_fft_sel s = a.fsel[i];
             if (!s.use_fft || s.poly == 2 || !poly_match(a.poly, s.poly)) return 0;
-            return jobs_of(g, s.hx, s.hy).per * C;
+            return jobs_of(g, s.hx, s.hy, kTall && s.poly == 1 && s.pad_[0] != 0).per * C;
         };
         bool work = false;
         int base = 0;
@@ -765,8 +976,9 @@ __global__ __launch_bounds__(64, 2) void conv_wfft_kernel(const ConvPass a, cons
         img = __builtin_amdgcn_readfirstlane(img); rem = __builtin_amdgcn_readfirstlane(rem);
         hx = as_constant(a.fsel + img)->hx; hy = as_constant(a.fsel + img)->hy;
         fold = a.poly == 2 && as_constant(a.fsel + img)->poly != 0;
+        tall = kTall && as_constant(a.fsel + img)->poly == 1 && as_constant(a.fsel + img)->pad_[0] != 0;
     }
-    const WJobs j = jobs_of(g, hx, hy);
+    const WJobs j = jobs_of(g, hx, hy, tall);
     const int pl = __builtin_amdgcn_readfirstlane(div_rcp(rem, __builtin_amdgcn_rcpf((float)j.per)));
     if (pl >= C) return;                               // (one image: positions beyond its planes)
     const int pair = q * j.per + (rem - pl * j.per);
@@ -777,6 +989,9 @@ __global__ __launch_bounds__(64, 2) void conv_wfft_kernel(const ConvPass a, cons
     const pb_blur_info *info = a.info + img;
     if (a.ring && !ring_live(a, ty, pxi, hx, hy)) return;
     const ConvPass af = fold_pass(a, fold);
+    if constexpr (kTall) {
+        if (tall) { wave_tall(af, plane, ty, pxi, hx, hy, zb, kp); return; }
+    }
     if (taper_is_copy(af, ty, pxi, hx, hy)) { copy_pair<TX, TOut>(af, plane, ty, pxi, hx, hy); return; }
     if (pair_is_fast<TIn, TX, TOut>(af, ty, pxi, hx, hy)) wave_pair<1, TIn, TX, TOut, ZERO>(af, info, plane, ty, pxi, hx, hy, zb, kp, tr);
     else if (pair_is_gen<TIn, TX, TOut>(af, pxi, hx)) wave_pair<2, TIn, TX, TOut, ZERO>(af, info, plane, ty, pxi, hx, hy, zb, kp, tr);
@@ -786,7 +1001,7 @@ __global__ __launch_bounds__(64, 2) void conv_wfft_kernel(const ConvPass a, cons
 // The output extent of a pass and the largest job list its records may ask for: `poly2` = the records may carry one-pass
 // images with the composite filter's halos (PolySpec.on == 2: tiles down to PB_POLY_MIN_TX x PB_POLY_MIN_TY, but never
 // smaller in area than the cost model of khat.h admits); otherwise halos are at most 12.  (Counts stay below 2^20: the kernel divides with reciprocals.)
-bool wfft_geometry(const ConvPass &p, bool poly2, float min_area, WGeom &g, long &per_max) {
+bool wfft_geometry(const ConvPass &p, bool poly2, bool tall, float min_area, WGeom &g, long &per_max) {
     g.oh = (p.out_kind == OUT_INTERIOR) ? p.H : p.H + 2 * p.pad;
     g.ow = (p.out_kind == OUT_INTERIOR) ? p.W : p.W + 2 * p.pad;
     per_max = 0;
@@ -797,6 +1012,15 @@ bool wfft_geometry(const ConvPass &p, bool poly2, float min_area, WGeom &g, long
             const bool one = poly2 && tx >= PB_POLY_MIN_TX && ty >= PB_POLY_MIN_TY && (float)(tx * ty) >= min_area;
             if (!three && !one) continue;
             const long nj = (long)(((g.ow + tx - 1) / tx + 1) / 2) * ((g.oh + ty - 1) / ty);
+            if (nj > (1L << 20)) return false;
+            per_max = std::max(per_max, (nj + 7) / 8);
+        }
+        // (one-pass images on windows 64 wide and 128 tall, PolySpec.tall: single windows, tiles of tx by 128 - 2 hy, row halos of
+        // their own range)
+        for (int hy = 2; poly2 && tall && hy <= PB_TALL_MAX_HY; hy += 2) {
+            const int tx = FT_N - 2 * hx, tyt = 2 * FT_N - 2 * hy;
+            if (tx < PB_POLY_MIN_TX || tx * tyt < PB_TALL_MIN_AREA) continue;
+            const long nj = (long)((g.ow + tx - 1) / tx) * ((g.oh + tyt - 1) / tyt);
             if (nj > (1L << 20)) return false;
             per_max = std::max(per_max, (nj + 7) / 8);
         }
@@ -832,7 +1056,7 @@ extern "C" int pb_debug_wf_trace(unsigned long long *host, int n_waves) {
 // (as pb_conv_w128_feasible: the largest job list a pass with one-pass images of the smallest tiles may need)
 bool pb_conv_wfft_feasible(const ConvPass &p, bool poly2) {
     WGeom g; long per_max = 0;
-    return wfft_geometry(p, poly2, (float)PB_POLY_MIN_AREA, g, per_max);
+    return wfft_geometry(p, poly2, poly2 && p.boundary == PB_WRAP, (float)PB_POLY_MIN_AREA, g, per_max);
 }
 
 bool pb_conv_wfft_types(const ConvPass &p) {
@@ -854,7 +1078,8 @@ int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p) {
     const float min_area = (float)PB_POLY_MIN_AREA;        // (the smallest one-pass tile the cost model of khat.h admits)
     WGeom g;
     long per_max = 0;
-    if (!wfft_geometry(p, poly2, min_area, g, per_max)) {
+    const bool tall = poly2 && pb_spec_of_spectra(ctx, p.khat).tall != 0;
+    if (!wfft_geometry(p, poly2, tall, min_area, g, per_max)) {
         if (poly2) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "conv pass: too many windows for the tile-spectrum body");
         return PB_ERR_UNSUPPORTED;
     }
@@ -867,8 +1092,10 @@ int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p) {
             const pb_fft_sel &e = (*ctx->known_sel)[(size_t)b];
             const bool takes = e.use_fft && e.poly != 2 && (p.poly == 2 || (e.poly != 0) == (p.poly != 0));      // (poly_match, conv_fft_common.h)
             if (!takes) continue;
-            const int tx = FT_N - 2 * e.hx, ty = FT_N - 2 * e.hy;
-            const long nj = (long)(((g.ow + tx - 1) / tx + 1) / 2) * ((g.oh + ty - 1) / ty);
+            const bool et = tall && e.poly == 1 && e.pad_[0] != 0;      // (single windows 64 wide and 128 tall: wave_tall)
+            const int tx = FT_N - 2 * e.hx, ty = (et ? 2 * FT_N : FT_N) - 2 * e.hy;
+            const long tiles_x = (g.ow + tx - 1) / tx;
+            const long nj = (et ? tiles_x : (tiles_x + 1) / 2) * ((g.oh + ty - 1) / ty);
             per_sum += (nj + 7) / 8; jobs += nj * p.C;
         }
         if (!jobs) return PB_OK;                            // nothing in this launch for any image

@@ -206,7 +206,7 @@ __device__ __forceinline__ void khat_body(const pb_blur_info *info, float *out, 
     const int R = rl ? rl->radius : info->radius;
     const int separable = rl ? rl->separable : info->separable;
     if (tid < KH_FT_N) { cs[tid] = kCos64[tid]; sn[tid] = kSin64[tid]; }
-    if (ps.on == 3 && tid >= 64 && tid < 192) { c8[tid - 64] = kCos128[tid - 64]; s8[tid - 64] = kSin128[tid - 64]; }   // (for khat128_body: requested here, met by the barriers below)
+    if ((ps.on == 3 || ps.tall) && tid >= 64 && tid < 192) { c8[tid - 64] = kCos128[tid - 64]; s8[tid - 64] = kSin128[tid - 64]; }   // (for khat128_body and the 64 x 128 grid: requested here, met by the barriers below)
     bool sym = true;
     // (the short chain: the taps are the caller's LDS array as it is -- full support, nothing outside the box to mask -- and
     // point-symmetric by construction, PolySpec.always)
@@ -313,7 +313,7 @@ __device__ __forceinline__ void khat_body(const pb_blur_info *info, float *out, 
     // image would take otherwise -- three passes over windows with the kernel's halos (window counts compared; a one-pass
     // window needs no x operand, and the pass moves 2 words per sample instead of 8: `gain`), or the stencil bodies
     // (`min_area`: the tile area from which one window pass beats three stencil passes).
-    bool poly = false, poly128 = false;
+    bool poly = false, poly128 = false, tall = false;
     if (ps.on == 1) poly = symm && Rh <= 4 && max(hxp, hyp) <= 12;
     if (ps.on >= 2 && symm) {
         const int txp = KH_FT_N - 2 * hxp, typ = KH_FT_N - 2 * hyp;
@@ -326,8 +326,15 @@ __device__ __forceinline__ void khat_body(const pb_blur_info *info, float *out, 
         if (txp >= PB_POLY_MIN_TX && typ >= PB_POLY_MIN_TY && txp * typ >= ps.min_area) c64 = 1.f / (float)(txp * typ);
         const int tx8 = 2 * KH_FT_N - 2 * hxp, ty8 = 2 * KH_FT_N - 2 * hyp;
         if (ps.on == 3 && ps.cost128 > 0.f && tx8 >= PB_POLY128_MIN_T && ty8 >= PB_POLY128_MIN_T) c128 = ps.cost128 / (float)(tx8 * ty8);
-        poly128 = c128 < c64 && c128 < c3;
-        poly = poly128 || c64 <= c3;
+        // windows 64 wide and 128 tall (PolySpec.tall: the host vouches for the planes and the boundary): the row halo is paid once
+        // for what two 64 x 64 windows keep -- priced in the same units, a 64 x 64 pair being 2 / (2 Tx Ty)
+        float ctall = INFINITY;
+        const bool tall_ok = ps.tall != 0 && txp >= PB_POLY_MIN_TX && hyp <= PB_TALL_MAX_HY && txp * (2 * KH_FT_N - 2 * hyp) >= PB_TALL_MIN_AREA;
+        // (a pair job keeps 2 Tx Ty samples for 1, i.e. costs 1 / (Tx Ty) per TWO samples; a tall job keeps Tx (128 - 2 hy) for cost_tall)
+        if (tall_ok) ctall = 2.f * ps.cost_tall / (float)(txp * (2 * KH_FT_N - 2 * hyp));
+        tall = tall_ok && (ps.tall == 2 || (ctall < c64 && ctall < c128 * (PB_POLY_COST128_BARE / PB_POLY_COST128) && ctall < c3));
+        poly128 = !tall && c128 < c64 && c128 < c3;
+        poly = poly128 || tall || c64 <= c3;
     }
     const bool use = poly || use3;
     if (tid == 0 && slice == 0) {
@@ -336,7 +343,7 @@ __device__ __forceinline__ void khat_body(const pb_blur_info *info, float *out, 
         sel->hx = poly ? hxp : hxk; sel->hy = poly ? hyp : hyk;
         if (!lean) sel->strip = (separable != 0 && R > 8) ? 1 : 0;
         sel->poly = poly128 ? 2 : (poly ? 1 : 0);
-        sel->pad_[0] = 0;
+        sel->pad_[0] = tall ? 1 : 0;                 // (the one pass runs on windows 64 wide and 128 tall: conv_wfft.hip)
         if (!lean) sel->pad_[1] = 0;                 // (lean: the record workgroup's word -- 1 = taps not point-symmetric)
     }
     PB_PT(23);
@@ -358,6 +365,36 @@ __device__ __forceinline__ void khat_body(const pb_blur_info *info, float *out, 
     }
     __syncthreads();
     PB_PT(21);
+    if (tall) {
+        // The polynomial's spectrum on the grid of a window 64 wide and 128 tall, as wave_tall (conv_wfft.hip) reads it: [x position]
+        // [lane], lane l >= 1 = row frequency (l >> 3) + 8 (l & 7) of 128 -- 1 .. 63 --, and lane 0 the two real rows 0 and 64, which
+        // share one transform there: their half sum Hs in lane 0's column, their half difference Hd in 64 values behind the 64 x 64
+        // array.  The same sums in double as below; both transforms' normalisation and the factor 4 of the real-input split and
+        // merge folded in.
+        for (int idx = tid; idx < PXS * KH_FT_N; idx += KH_THREADS) {
+            const int pxl = idx >> 6, py = idx & 63, fy = (py >> 3) + 8 * (py & 7);
+            auto at = [&](int f) {
+                double ar = 0.5 * G[pxl].x;
+#pragma unroll 4
+                for (int u = 1; u < NR; ++u) {
+                    const int m = (f * u) & 127;
+                    const double2 g = G[u * PXS + pxl];
+                    ar += g.x * c8[m] - g.y * s8[m];
+                }
+                const double v = 2.0 * ar;
+                return ((((double)ps.a3 * v + (double)ps.a2) * v + (double)ps.a1) * v + (double)ps.b) * (1.0 / 16384.0);
+            };
+            if (py) {
+                out[(px0 + pxl) * KH_FT_N + py] = (float)at(fy);
+            } else {
+                const double h0 = at(0), h64 = at(64);
+                out[(px0 + pxl) * KH_FT_N] = (float)(0.5 * (h0 + h64));
+                out[KH_FT_N * KH_FT_N + px0 + pxl] = (float)(0.5 * (h0 - h64));
+            }
+        }
+        PB_PT(22);
+        return;
+    }
     for (int idx = tid; idx < PXS * KH_FT_N; idx += KH_THREADS) {          // stored transposed: [x position][y position]
         const int pxl = idx >> 6, py = idx & 63, fy = (py >> 3) + 8 * (py & 7);
         double ar = 0.5 * G[pxl].x;
