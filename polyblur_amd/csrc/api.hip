@@ -89,6 +89,8 @@ static int pitch4(int w) { return (w + 3) & ~3; }
 //   PB_FFT_FIRST / _ROWS=0|r    the column / row transform's first and last stage: the greedy plan's order, or radix r (default: by line length)
 //   PB_COLS_FIXED=0, PB_ROWS_FIXED=0   the line transforms always by the run-time-plan kernels (estimate.hip), also where
 //                               lines_fixed.hip holds the plan (the tests' bit-identity reference)
+//   PB_POLY_ONE_LAUNCH=0|2      the window pass of a polynomial on device-built records as two launches, one per window form (default 1:
+//                               one launch, conv_win.hip); 2 = host-built records take the one launch too (tools/one_launch_timing.py)
 //   PB_POLY_TALL=0|2            one-pass images never / wherever admitted on windows 64 wide and 128 tall (default 1: by the cost model)
 //   PB_STRIP=1                  a measured experiment (conv_strip.hip): read in --experimental builds only
 // A knob stays while a test, bench.py or a script under tools/ names it.  Retired, their alternatives measured and dropped in
@@ -105,7 +107,7 @@ static void pb_read_knobs(pb_ctx *ctx) {
 #endif
     geti("PB_EST_GRAY_ROWS", ctx->est_gray_rows); geti("PB_EST_LEAN", ctx->est_lean); geti("PB_DT_ROWS_REG", ctx->dt_rows_reg); geti("PB_DT_COLS_STRIP", ctx->dt_cols_strip); geti("PB_DT_COLS_COOP", ctx->dt_cols_coop);
     geti("PB_FFT_EXT_RADIX", ctx->fft_ext_radix); geti("PB_FFT_FIRST", ctx->fft_first); geti("PB_FFT_FIRST_ROWS", ctx->fft_first_rows); geti("PB_COLS_FIXED", ctx->cols_fixed); geti("PB_ROWS_FIXED", ctx->rows_fixed);
-    geti("PB_POLY1", ctx->poly_mode); geti("PB_POLY_TALL", ctx->poly_tall);
+    geti("PB_POLY1", ctx->poly_mode); geti("PB_POLY_TALL", ctx->poly_tall); geti("PB_POLY_ONE_LAUNCH", ctx->poly_one_launch);
     geti("PB_POLY_ALWAYS", ctx->poly_always); geti("PB_POLY_PADDED", ctx->poly_padded); geti("PB_TAPER_RING", ctx->taper_ring); geti("PB_ZERO_RING", ctx->zero_ring); getl("PB_ZERO_RING_MIN_PAIRS", ctx->zero_ring_min_pairs);
 }
 

@@ -183,6 +183,7 @@ struct pb_ctx {
     int cols_fixed = 1;                  // env PB_COLS_FIXED: 0 = the column transform always by the run-time-plan kernel (grad_cols_kernel), also where lines_fixed.hip holds the plan
     int rows_fixed = 1;                  // env PB_ROWS_FIXED: the same for the row transforms (gray_rows_kernel / grad_rows_kernel)
     size_t phase_budget = 0;             // pb_set_phase_budget: bytes of complex scratch one group of plane pairs of the pure-phase polynomial may take (conv_phase.hip); 0 = 256 MiB.  One pair is always allowed
+    int poly_one_launch = 1;             // env PB_POLY_ONE_LAUNCH: 0 = the window pass of a PolySpec.always polynomial as two launches (conv_w128.hip, conv_wfft.hip) instead of one (conv_win.hip); 2 = host-built records take the one launch too (tools/one_launch_timing.py)
     int poly_tall = 1;                   // env PB_POLY_TALL: one-pass images on windows 64 wide and 128 tall -- 0 = never, 1 = where the cost model of khat.h prices them lowest, 2 = every image the form admits
     int strip_mode = 0;                  // env PB_STRIP: 1 = rank-1 kernels of full support take the streaming strip body (fp32 planes; --experimental builds only)
 };
@@ -317,6 +318,8 @@ int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p);                     // 
 bool pb_conv_fft_types(const ConvPass &p);                                   // conv_fft.hip: whether the workgroup form is built for the pass's types
 bool pb_conv_wfft_types(const ConvPass &p);
 int pb_launch_conv_w128(pb_ctx *ctx, const ConvPass &p);                     // conv_w128.hip: the one-pass polynomial on 128 x 128 windows (pb_fft_sel.poly == 2)
+int pb_launch_conv_win(pb_ctx *ctx, const ConvPass &p);                      // conv_win.hip: the one window pass of every image, 128 x 128 or 64-wide windows by its record, in ONE launch; PB_ERR_UNSUPPORTED: types not built
+bool pb_conv_win_types(const ConvPass &p);                                   // ... whether it is built for this composite pass
 bool pb_conv_w128_feasible(const ConvPass &p);                               // ... and whether its worst-case job list fits the grid
 bool pb_conv_wfft_feasible(const ConvPass &p, bool poly2);                   // conv_wfft.hip: likewise for the wave form
 bool pb_conv_w128_types(int in_dtype, int out_dtype);                                  // ... whether it is built for the pass's types

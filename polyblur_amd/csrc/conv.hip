@@ -587,12 +587,23 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
     // image of up to 4K runs everything on the caller's stream (measured: 4K 0.738 -> 0.722 ms of device time per call, while
     // 32 x 1080p would go from 6.09 to 6.61 ms without the side stream).
     // PolySpec.always (records of the estimation, nothing the host has read back): every image takes one window pass, on 64 x 64
-    // or on 128 x 128 windows -- two launches on the caller's stream, each skipping the other's images, and nothing else.
+    // or on 128 x 128 windows -- one launch on the caller's stream whose workgroups run either body (two launches, each skipping
+    // the other's images, before conv_win.hip: the empty one cost a 4K call 3.5 - 5.8 us per iteration), and nothing else.
     if (poly_on && ctx->poly_want.always && !have) {
         float *k = nullptr; pb_fft_sel *sel = nullptr;
         int rc = pb_build_khat(ctx, info, B, &k, &sel, !by_estimate);
         if (rc) return rc;
         auto window_pass = [&]() -> int {
+            // one launch carries both window forms (conv_win.hip) where it is built for the composite's types; PB_POLY_ONE_LAUNCH=0,
+            // or types it is not built for: the two launches, each skipping the other's images
+            if (ctx->poly_one_launch && ctx->fft_wave && ctx->poly_want.on == 3) {
+                ConvPass pc = whole;
+                pc.khat = k; pc.fsel = sel;
+                if (pb_conv_win_types(pc)) {
+                    if (!fft_pass_ok(pc)) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "one-pass polynomial: composite pass not feasible");
+                    return pb_launch_conv_win(ctx, pc);
+                }
+            }
             const int e = composite128(k, sel);
             if (e) return e;
             if (pb_conv_wfft_types(whole)) return composite(k, sel);
@@ -636,6 +647,24 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
             if (!rc) rc = first_two();
         }
         return rc ? rc : ring_steps(2, 3);
+    }
+    // Lab switch of tools/one_launch_timing.py (PB_POLY_ONE_LAUNCH=2): host-built records whose every image takes one window pass
+    // go through the merged launch too, with the exact grid -- what the pipeline's launch costs, without the estimation around it.
+    if (poly_on && have && ctx->poly_one_launch == 2 && ctx->fft_wave && ctx->poly_want.on == 3 && steps[0].boundary != PB_ZERO) {
+        const std::vector<pb_fft_sel> *ksel = nullptr;
+        const pb_ctx::BodyFlags *kf = known_flags(ctx, info, B, &ksel);
+        if (kf && ksel && kf->any_fft && !kf->any_other && !kf->any_fft3 && pb_conv_win_types(whole)) {
+            ConvPass pc = whole;
+            float *k = nullptr; pb_fft_sel *sel = nullptr;
+            int rc = pb_build_khat(ctx, info, B, &k, &sel, !held);
+            if (rc) return rc;
+            pc.khat = k; pc.fsel = sel;
+            if (!fft_pass_ok(pc)) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "one-pass polynomial: composite pass not feasible");
+            ctx->known_sel = ksel;
+            rc = pb_launch_conv_win(ctx, pc);
+            ctx->known_sel = nullptr;
+            return rc;
+        }
     }
     constexpr long min_side_tiles = 12288;      // (a 4K image has 6405 stencil tiles, 32 x 1080p 53568)
     const long stencil_tiles = (long)((steps[0].H + 2 * steps[0].pad + 63) / 64) * ((steps[0].W + 2 * steps[0].pad + 63) / 64) * steps[0].P;
