@@ -333,6 +333,35 @@ int pb_inverse_filter_phase_taps(pb_ctx *ctx, const void *in, void *out, int dty
                                  const pb_taps *taps, float alpha, float beta, int edgetaping, int remove_halo,
                                  const float *grad0_x, const float *grad0_y);
 
+/* ---- gradients of the non-blind step.  The reference's README ("Import into your projects") promises: "The module and the
+ * functional version above are fully differentiable.  They thus can be put within neural networks as training losses" -- there
+ * ATen's autograd differentiates filters.convolve2d and deblurring.compute_polynomial; here these three calls are their backward
+ * passes.  ODD kh and kw only (PB_ERR_UNSUPPORTED otherwise: the adjoint of an even-sized kernel sits one sample off the two forms a
+ * set holds).  All planes (B,C,H,W) float32 that are the whole domain; outputs may not alias inputs.
+ *
+ * pb_tap_gradient: the lag correlation behind every tap gradient -- dev_grad[b][i][j] (= when accumulate == 0, += otherwise)
+ * scale * sum over the C planes of image b and over every sample p of u[p] * v[p + off(i, j)], off(i, j) = (i - kh/2, j - kw/2)
+ * with v zero outside the domain (PB_ZERO) or (kh/2 - i, kw/2 - j) with indices modulo the domain (PB_WRAP): d loss / d taps of
+ * out = pb_convolve2d_taps(v) (filters.py:14-37) for the upstream gradient u.  1 <= kh, kw <= 49; no fit check (lags may exceed
+ * the domain).  dev_grad: DEVICE memory, (B,kh,kw).  fp32 sums in a fixed order, no atomics: the same call gives the same bits.  */
+int pb_tap_gradient(pb_ctx *ctx, const float *u, const float *v, int B, int C, int H, int W, int kh, int kw,
+                    int boundary, float scale, int accumulate, float *dev_grad);
+
+/* Backward of pb_convolve2d_taps (filters.convolve2d, filters.py:14-37): grad_x = K^T grad_out -- the same pass with the set's
+ * other orientation --, grad_taps (device, (B,kh,kw)) = the lag correlation of grad_out with x.  grad_x or grad_taps may be NULL,
+ * not both; x may be NULL when grad_taps is.  The argument rules and refusals of pb_convolve2d_taps.                          */
+int pb_convolve2d_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps,
+                                int B, int C, int H, int W, const pb_taps *taps, int boundary);
+
+/* Backward of pb_compute_polynomial_taps with not_symmetric == 0 (deblurring.compute_polynomial, deblurring.py:113-169;
+ * the pure-phase variant has no backward).  With g = grad_out, g2 = K^T g, g1 = K^T g2:
+ *   grad_x = b g + a1 g2 + a2 g1 + a3 K^T g1 -- the same polynomial of K^T, in whichever form the forward would take;
+ *   grad_taps (device, (B,kh,kw)) = L(g, t2) + L(g2, t1) + L(g1, a3 x) with the forward's temporaries t1, t2 formed again by
+ *   explicit Horner steps (context scratch: four plane sets of the domain, "grad.t1" .. "grad.g1", and the partial tables).
+ * NULL rules as above.  The argument rules and refusals of pb_compute_polynomial_taps.                                        */
+int pb_compute_polynomial_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps,
+                                        int B, int C, int H, int W, const pb_taps *taps, float alpha, float beta, int boundary);
+
 /* The pure-phase polynomial takes the plane pairs of an image in groups whose complex scratch (one Hp x Wp float2 plane per
  * pair) stays within `bytes`; one pair is always allowed.  0 = the default, 256 MiB.  Results do not depend on it.       */
 int pb_set_phase_budget(pb_ctx *ctx, size_t bytes);

@@ -1143,6 +1143,29 @@ int taps_geometry(pb_ctx *ctx, const pb_taps *t, int B, int C, int H, int W, int
 
 int taps_pass(pb_ctx *ctx, const Geometry &g, const ConvPass &p) { return g.big.taps ? pb_launch_conv_big(ctx, p, g.big) : pb_launch_conv(ctx, p); }
 
+// The adjoint of a pass with an ODD-sized kernel is the same form under the same boundary with the taps reflected inside their
+// kh x kw array -- and the set already holds that orientation as the OTHER boundary's form (records: embed_taps(reflect); tables:
+// caller_taps_kernel's wrap[iy][ix] = raw[kh/2 - iy][kw/2 - ix] = zero[-iy][-ix] when (kh - 1) / 2 == kh / 2).  An even side moves the
+// centre by one sample in the adjoint: refused by the callers.
+void taps_adjoint(const pb_taps *t, int boundary, Geometry *g, const pb_blur_info **recs) {
+    if (t->tables) { g->big = boundary == PB_WRAP ? t->big_zero : t->big_wrap; *recs = nullptr; }
+    else *recs = boundary == PB_WRAP ? t->rec_zero : t->rec_wrap;
+}
+
+// what both backward calls check before any device work
+int backward_args(pb_ctx *ctx, const char *who, const float *x, const float *grad_out, const float *grad_x, const float *grad_taps,
+                  const pb_taps *taps) {
+    if (!grad_out) return pb_fail(ctx, PB_ERR_BADARG, "%s: grad_out is null", who);
+    if (!grad_x && !grad_taps) return pb_fail(ctx, PB_ERR_BADARG, "%s: grad_x and grad_taps are both null", who);
+    if (grad_taps && !x) return pb_fail(ctx, PB_ERR_BADARG, "%s: the tap gradient needs x", who);
+    if ((grad_x && (grad_x == grad_out || grad_x == x)) || (grad_taps && (grad_taps == grad_out || grad_taps == x || grad_taps == grad_x)))
+        return pb_fail(ctx, PB_ERR_BADARG, "%s: an output aliases an input", who);
+    if (taps && (!(taps->kh & 1) || !(taps->kw & 1)))
+        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "%s: a %d x %d kernel -- the adjoint of an even side sits one sample off the forms the set holds: "
+                       "odd sides only", who, taps->kh, taps->kw);
+    return PB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1339,6 +1362,92 @@ int pb_compute_polynomial_taps(pb_ctx *ctx, const float *in, float *out, int B, 
     float *t2 = static_cast<float *>(pb_scratch(ctx, "inv.t2", sizeof(float) * g.P * g.pplane));
     if (!t1 || !t2) return PB_ERR_NOMEM;
     return run_polynomial(ctx, g, in, PB_F32, in, recs, alpha, beta, boundary, t1, t2, out, PB_F32, 0);
+}
+
+int pb_tap_gradient(pb_ctx *ctx, const float *u, const float *v, int B, int C, int H, int W, int kh, int kw, int boundary, float scale,
+                    int accumulate, float *dev_grad) {
+    int rc = check_shape(ctx, PB_F32, B, C, H, W);
+    if (rc) return rc;
+    if (!u || !v || !dev_grad || dev_grad == u || dev_grad == v) return pb_fail(ctx, PB_ERR_BADARG, "pb_tap_gradient: null or aliased argument");
+    if (boundary != PB_WRAP && boundary != PB_ZERO) return pb_fail(ctx, PB_ERR_BADARG, "bad boundary");
+    if (kh < 1 || kw < 1) return pb_fail(ctx, PB_ERR_BADARG, "pb_tap_gradient: a %d x %d kernel", kh, kw);
+    if (kh > PB_KSIZE_MAX || kw > PB_KSIZE_MAX)
+        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "a %d x %d kernel: sizes up to %d x %d are built", kh, kw, PB_KSIZE_MAX, PB_KSIZE_MAX);
+    if (!(kh & 1) || !(kw & 1)) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "pb_tap_gradient: a %d x %d kernel -- odd sides only", kh, kw);
+    PB_HIP(hipSetDevice(ctx->device));
+    return pb_launch_tap_gradient(ctx, u, v, B, C, H, W, kh, kw, boundary, scale, accumulate, dev_grad);
+}
+
+int pb_convolve2d_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps, int B, int C, int H,
+                                int W, const pb_taps *taps, int boundary) {
+    int rc = check_shape(ctx, PB_F32, B, C, H, W);
+    if (rc) return rc;
+    rc = backward_args(ctx, "pb_convolve2d_taps_backward", x, grad_out, grad_x, grad_taps, taps);
+    if (rc) return rc;
+    Geometry g; const pb_blur_info *recs = nullptr;
+    rc = taps_geometry(ctx, taps, B, C, H, W, boundary, true, true, &g, &recs);
+    if (rc) return rc;
+    PB_HIP(hipSetDevice(ctx->device));
+    g.pp = W; g.pplane = g.HW;
+    if (grad_x) {
+        // grad_x = K^T grad_out: the same pass with the set's other orientation
+        taps_adjoint(taps, boundary, &g, &recs);
+        ConvPass p = base_pass(g, recs, boundary);
+        set_in_padded(p, g, grad_out); set_x_padded(p, g, grad_out); set_out_padded(p, g, grad_x);
+        rc = taps_pass(ctx, g, p);
+        if (rc) return rc;
+    }
+    if (grad_taps) return pb_launch_tap_gradient(ctx, grad_out, x, B, C, H, W, taps->kh, taps->kw, boundary, 1.f, 0, grad_taps);
+    return PB_OK;
+}
+
+int pb_compute_polynomial_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps, int B, int C,
+                                        int H, int W, const pb_taps *taps, float alpha, float beta, int boundary) {
+    int rc = check_shape(ctx, PB_F32, B, C, H, W);
+    if (rc) return rc;
+    rc = backward_args(ctx, "pb_compute_polynomial_taps_backward", x, grad_out, grad_x, grad_taps, taps);
+    if (rc) return rc;
+    Geometry g; const pb_blur_info *recs = nullptr;
+    rc = taps_geometry(ctx, taps, B, C, H, W, boundary, true, false, &g, &recs);
+    if (rc) return rc;
+    PB_HIP(hipSetDevice(ctx->device));
+    g.pp = W; g.pplane = g.HW;
+    Geometry ga = g; const pb_blur_info *arecs = nullptr;
+    taps_adjoint(taps, boundary, &ga, &arecs);
+    if (grad_taps) {
+        // grad_k = L(g, t2) + L(g2, t1) + L(g1, t0), t0 = a3 x, g2 = K^T g, g1 = K^T g2: the forward's two temporaries are formed
+        // again, step by step (pb_launch_conv_poly would fold the three steps into one window pass and never write them)
+        const size_t bytes = sizeof(float) * g.P * g.HW;
+        float *t1 = static_cast<float *>(pb_scratch(ctx, "grad.t1", bytes)), *t2 = static_cast<float *>(pb_scratch(ctx, "grad.t2", bytes));
+        float *g2 = static_cast<float *>(pb_scratch(ctx, "grad.g2", bytes)), *g1 = static_cast<float *>(pb_scratch(ctx, "grad.g1", bytes));
+        if (!t1 || !t2 || !g2 || !g1) return PB_ERR_NOMEM;
+        ConvPass steps[3];
+        make_steps(g, x, PB_F32, x, recs, alpha, beta, boundary, t1, t2, g1, PB_F32, 0, steps);      // (steps[2], y itself, is not run)
+        for (int s = 0; s < 2; ++s) {
+            rc = taps_pass(ctx, g, steps[s]);
+            if (rc) return rc;
+        }
+        ConvPass p = base_pass(ga, arecs, boundary);
+        set_in_padded(p, ga, grad_out); set_x_padded(p, ga, grad_out); set_out_padded(p, ga, g2);
+        rc = taps_pass(ctx, ga, p);
+        if (rc) return rc;
+        set_in_padded(p, ga, g2); set_x_padded(p, ga, g2); set_out_padded(p, ga, g1);
+        rc = taps_pass(ctx, ga, p);
+        if (rc) return rc;
+        const float a3 = alpha / 2 - beta + 2;
+        rc = pb_launch_tap_gradient(ctx, grad_out, t2, B, C, H, W, taps->kh, taps->kw, boundary, 1.f, 0, grad_taps);
+        if (!rc) rc = pb_launch_tap_gradient(ctx, g2, t1, B, C, H, W, taps->kh, taps->kw, boundary, 1.f, 1, grad_taps);
+        if (!rc) rc = pb_launch_tap_gradient(ctx, g1, x, B, C, H, W, taps->kh, taps->kw, boundary, a3, 1, grad_taps);
+        if (rc) return rc;
+    }
+    if (grad_x) {
+        // grad_x = b g + a1 K^T g + a2 K^T^2 g + a3 K^T^3 g: the same polynomial of the adjoint, in whichever form run_polynomial picks
+        const size_t pbytes = sizeof(float) * ga.P * ga.pplane;
+        float *t1 = static_cast<float *>(pb_scratch(ctx, "inv.t1", pbytes)), *t2 = static_cast<float *>(pb_scratch(ctx, "inv.t2", pbytes));
+        if (!t1 || !t2) return PB_ERR_NOMEM;
+        return run_polynomial(ctx, ga, grad_out, PB_F32, grad_out, arecs, alpha, beta, boundary, t1, t2, grad_x, PB_F32, 0);
+    }
+    return PB_OK;
 }
 
 }  // extern "C"

@@ -352,6 +352,14 @@ struct PhaseCall {
 int pb_launch_phase(pb_ctx *ctx, const PhaseCall &c);
 int pb_phase_sides_supported(pb_ctx *ctx, int Hp, int Wp);                   // PB_ERR_UNSUPPORTED (message set) unless both sides' lines fit LDS
 
+// the gradient of a pass with respect to its taps (conv_grad.hip): grad[b][i][j] (= or +=, `accumulate`) scale * the lag
+// correlation of u with v over the C planes of image b -- (B,C,H,W) fp32 planes that are the whole domain, kh and kw odd, v zero
+// outside the domain (PB_ZERO) or circular over it (PB_WRAP), taps indexed as pb_taps_create places them under that boundary.
+// Partial tables in the scratch "grad.partial": B * pb_tap_gradient_groups * kh * kw floats
+int pb_launch_tap_gradient(pb_ctx *ctx, const float *u, const float *v, int B, int C, int H, int W, int kh, int kw, int boundary,
+                           float scale, int accumulate, float *grad);
+int pb_tap_gradient_groups(int B, int C, int H, int W);
+
 // ------------------------------------------------------------------------------------
 // estimation (estimate.hip)
 // ------------------------------------------------------------------------------------

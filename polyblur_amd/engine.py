@@ -313,6 +313,27 @@ class Engine:
         self._check(self.lib.pb_inverse_filter_phase_taps(self.ctx, in_ptr, out_ptr, dtype, B, Cc, H, W, ks.handle, float(alpha),
                                                           float(beta), int(bool(edgetaping)), int(bool(remove_halo)), g0x_ptr, g0y_ptr))
 
+    # ---- backward passes of the two above (README: "fully differentiable"); odd kernel sides only -----------------------
+    def tap_gradient_ptr(self, u_ptr: int, v_ptr: int, shape, kh: int, kw: int, boundary, grad_ptr: int, scale=1.0, accumulate=False):
+        """grad (B,kh,kw; device) = or += scale * the lag correlation of u with v over each image's planes (pb_tap_gradient)"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_tap_gradient(self.ctx, u_ptr, v_ptr, B, Cc, H, W, int(kh), int(kw), int(boundary), float(scale),
+                                             int(bool(accumulate)), grad_ptr))
+
+    def convolve2d_taps_backward_ptr(self, x_ptr, grad_out_ptr: int, grad_x_ptr, grad_taps_ptr, shape, ks: KernelSet,
+                                     boundary=capi.PB_ZERO):
+        """grad_x_ptr or grad_taps_ptr may be None, not both; x_ptr may be None without grad_taps_ptr (pb_convolve2d_taps_backward)"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_convolve2d_taps_backward(self.ctx, x_ptr, grad_out_ptr, grad_x_ptr, grad_taps_ptr, B, Cc, H, W,
+                                                         ks.handle, int(boundary)))
+
+    def compute_polynomial_taps_backward_ptr(self, x_ptr, grad_out_ptr: int, grad_x_ptr, grad_taps_ptr, shape, ks: KernelSet, alpha,
+                                             beta, boundary=capi.PB_WRAP):
+        """the same for compute_polynomial(not_symmetric=False) (pb_compute_polynomial_taps_backward)"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_compute_polynomial_taps_backward(self.ctx, x_ptr, grad_out_ptr, grad_x_ptr, grad_taps_ptr, B, Cc, H, W,
+                                                                 ks.handle, float(alpha), float(beta), int(boundary)))
+
     def _taps_call(self, x: np.ndarray, call):
         x = np.ascontiguousarray(x)
         din = self.to_device("np.in", x)

@@ -25,6 +25,15 @@ be line lengths the engine holds in LDS (up to 20480 samples when every prime fa
 NotImplementedError before any device work otherwise.  Where |K| falls to fp32 roundoff (about 1e-7 -- a wide Gaussian has
 such bins near Nyquist) the phase of that filter is noise, in the reference as much as here: a property of the method.
 
+Gradients (the reference's README: "fully differentiable"): ``convolve2d``, ``compute_polynomial`` and
+``inverse_filtering_rank3`` return a tensor with a ``grad_fn`` when autograd is enabled and ``img`` or ``kernel`` is a tensor
+that requires grad -- with respect to the image and to the taps (not to alpha and b; no double backward).  The backward passes
+are the engine's too (pb_convolve2d_taps_backward, pb_compute_polynomial_taps_backward); the pad, crop and clamp of
+``inverse_filtering_rank3`` are then torch's own ops -- the replicate pad composed of slices, expand and cat, whose backward is
+an ordered sum where F.pad's adds with float atomics.  Under grad: float32 ROCm tensors and odd kernel sides only, and no
+``remove_halo``, ``do_edgetaper``, ``edgetaper()``, ``not_symmetric`` or ``inverse_filtering_nonsymmetric``
+(NotImplementedError before any device work).  Without grad nothing changes: the calls below run as before.
+
 The arithmetic is the HIP engine's (include/polyblur_hip.h: pb_taps_create and the *_taps calls); nothing runs on the CPU.
 """
 from __future__ import annotations
@@ -147,11 +156,128 @@ def _run(img, tensor, dt, shape, taps, per_plane, call, extra=()):
     return out
 
 
+def _wants_grad(img, kernel):
+    """autograd is on and the image or the kernel is a tensor that requires grad"""
+    ts = [t for t in (img, kernel) if _is_torch_tensor(t)]
+    if not ts:
+        return False
+    import torch
+    return torch.is_grad_enabled() and any(t.requires_grad for t in ts)
+
+
+def _refuse_under_grad(what, reason):
+    raise NotImplementedError("%s has no backward pass: %s" % (what, reason))
+
+
+def _check_grad(img, kernel, what):
+    """what the backward passes are built for -- raised before any device work"""
+    if _is_torch_tensor(img):
+        import torch
+        if img.dtype == torch.float16:
+            _refuse_under_grad(what + " of a float16 image", "gradients are built for float32 images")
+    kh, kw = (int(v) for v in kernel.shape[-2:])
+    if kh % 2 == 0 or kw % 2 == 0:
+        _refuse_under_grad(what + " with a %d x %d kernel" % (kh, kw), "the adjoint of an even kernel side sits one sample off centre -- odd sides only")
+    for name, t in (("img", img), ("kernel", kernel)):
+        if _is_torch_tensor(t) and t.requires_grad and not t.is_cuda:
+            _refuse_under_grad(what, "%s requires grad and is a CPU tensor -- gradients are built for ROCm tensors only" % name)
+    if not (_is_torch_tensor(img) and img.is_cuda):
+        _refuse_under_grad(what, "img is a CPU tensor or a NumPy array -- gradients are built for ROCm tensors only")
+
+
+def _replicate_pad(x, pad):
+    """F.pad(x, (pad,) * 4, mode='replicate') -- the same values, bit for bit -- composed of slices, expand and cat: the backward
+    of torch's own replicate pad adds the pad's gradients into the edge pixels with float atomics on the GPU, so two identical
+    backward calls differ in the last bits; the backward of expand is an ordered sum"""
+    import torch
+    B, C, H, W = x.shape
+    x = torch.cat([x[:, :, :1].expand(B, C, pad, W), x, x[:, :, -1:].expand(B, C, pad, W)], dim=2)
+    return torch.cat([x[..., :1].expand(B, C, H + 2 * pad, pad), x, x[..., -1:].expand(B, C, H + 2 * pad, pad)], dim=3)
+
+
+_TAPS_FUNCTION = None
+
+
+def _taps_function():
+    """the autograd.Function of both differentiable passes (made on first use: torch is imported lazily in this module)"""
+    global _TAPS_FUNCTION
+    if _TAPS_FUNCTION is not None:
+        return _TAPS_FUNCTION
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class TapsFunction(torch.autograd.Function):
+        """convolve2d (poly is None) or compute_polynomial (poly = (alpha, b)) of a ROCm float32 image that is the whole
+        domain.  taps: the (B', kh, kw) host array _check_kernel made of `kernel` (already rotated when `correlate`)."""
+
+        @staticmethod
+        def forward(ctx, img, kernel, taps, per_plane, bnd, poly, correlate):
+            shape = tuple(int(v) for v in img.shape)
+            if poly is None:
+                call = lambda eng, ks, i, o, s, ex: eng.convolve2d_taps_ptr(i, o, s, ks, bnd)
+            else:
+                call = lambda eng, ks, i, o, s, ex: eng.compute_polynomial_taps_ptr(i, o, s, ks, poly[0], poly[1], bnd, False)
+            x = img.detach()
+            out = _run(x, True, np.dtype(np.float32), shape, taps, per_plane, call)
+            ctx.save_for_backward(x)
+            ctx.pb = (taps, per_plane, bnd, poly, bool(correlate), shape)
+            ctx.kernel_like = kernel                        # (None: the kernel is an array)
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_out):
+            (x,) = ctx.saved_tensors
+            taps, per_plane, bnd, poly, correlate, shape = ctx.pb
+            want_x, want_k = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            B, C, H, W = shape
+            eshape = (B * C, 1, H, W) if per_plane else shape
+            dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+            eng = get_engine(dev)
+            xin = x.contiguous()
+            g = grad_out.detach().to(torch.float32).contiguous()
+            gx = torch.empty_like(xin) if want_x else None
+            gk = torch.empty(taps.shape, dtype=torch.float32, device=x.device) if want_k else None
+            with torch.cuda.device(dev):
+                eng.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+                ks = eng.set_taps(taps)
+                try:
+                    args = (xin.data_ptr(), g.data_ptr(), gx.data_ptr() if want_x else None, gk.data_ptr() if want_k else None, eshape, ks)
+                    if poly is None:
+                        eng.convolve2d_taps_backward_ptr(*args, bnd)
+                    else:
+                        eng.compute_polynomial_taps_backward_ptr(*args, poly[0], poly[1], bnd)
+                finally:
+                    ks.free()                               # (waits for the stream)
+            if want_k:
+                # back to kernel.shape: the taps were broadcast over the batch (summed here; the engine has summed over the
+                # planes of a one-channel kernel) and rotated for correlate=True (rotated back)
+                kernel = ctx.kernel_like
+                kb, kc, kh, kw = (int(v) for v in kernel.shape)
+                gk = gk.view(B, kc, kh, kw)
+                if kb == 1 and B > 1:
+                    gk = gk.sum(0, keepdim=True)
+                if correlate:
+                    gk = gk.flip(-2, -1)
+                gk = gk.to(device=kernel.device, dtype=kernel.dtype)
+            return gx, gk, None, None, None, None, None
+
+    _TAPS_FUNCTION = TapsFunction
+    return TapsFunction
+
+
+def _apply_taps_function(img, kernel, taps, per_plane, bnd, poly, correlate=False):
+    return _taps_function().apply(img, kernel if _is_torch_tensor(kernel) else None, taps, per_plane, bnd, poly, correlate)
+
+
 def convolve2d(img, kernel, method='direct'):
     """filters.convolve2d (filters.py:14-37) with a 2-D kernel: ``img`` is the whole domain."""
     tensor, shape, dt = _check_image(img, allow_half=False)
     taps, per_plane = _check_kernel(kernel, method, shape, pad_domain=False, circular_only=True)
     bnd = _BOUNDARY[method]
+    if _wants_grad(img, kernel):
+        _check_grad(img, kernel, "convolve2d")
+        return _apply_taps_function(img, kernel, taps, per_plane, bnd, None)
     return _run(img, tensor, dt, shape, taps, per_plane,
                 lambda eng, ks, i, o, s, ex: eng.convolve2d_taps_ptr(i, o, s, ks, bnd))
 
@@ -163,6 +289,8 @@ def edgetaper(img, kernel, n_tapers=3, method='fft'):
     if not isinstance(n_tapers, (int, np.integer)) or n_tapers < 0:
         raise ValueError("n_tapers must be an integer >= 0")
     taps, per_plane = _check_kernel(kernel, method, shape, pad_domain=False, circular_only=True)
+    if _wants_grad(img, kernel):
+        _refuse_under_grad("edgetaper", "the blends are not differentiated (call it under torch.no_grad() or on detached tensors)")
     bnd = _BOUNDARY[method]
     return _run(img, tensor, dt, shape, taps, per_plane,
                 lambda eng, ks, i, o, s, ex: eng.edgetaper_taps_ptr(i, o, s, ks, bnd, int(n_tapers)))
@@ -176,6 +304,18 @@ def inverse_filtering_rank3(img, kernel, alpha=2, b=4, correlate=False, remove_h
     tensor, shape, dt = _check_image(img, allow_half=True)
     taps, per_plane = _check_kernel(kernel, method, shape, pad_domain=True, circular_only=bool(do_edgetaper),
                                     correlate=bool(correlate))
+    if _wants_grad(img, kernel):
+        if remove_halo:
+            _refuse_under_grad("inverse_filtering_rank3(remove_halo=True)", "halo masking is not differentiated")
+        if do_edgetaper:
+            _refuse_under_grad("inverse_filtering_rank3(do_edgetaper=True)", "the edgetaper is not differentiated")
+        _check_grad(img, kernel, "inverse_filtering_rank3")
+        # pad, crop and clamp are torch's own ops with torch's own backward; the polynomial is the engine's
+        import torch
+        pad = taps.shape[-1] // 2
+        xp = _replicate_pad(img, pad)
+        y = _apply_taps_function(xp, kernel, taps, per_plane, _BOUNDARY[method], (alpha, b), bool(correlate))
+        return torch.clamp(y[..., pad:-pad, pad:-pad], 0.0, 1.0)
     extra = ()
     if remove_halo:
         _check_image_size(*shape[-2:])
@@ -214,6 +354,11 @@ def compute_polynomial(img, kernel, alpha, b, method='fft', not_symmetric=False)
     taps, per_plane = _check_kernel(kernel, method, shape, pad_domain=False, circular_only=False)
     if not_symmetric and method != "fft":
         raise ValueError("not_symmetric=True is the pure-phase filter of method='fft' (the reference's direct form ignores the flag)")
+    if _wants_grad(img, kernel):
+        if not_symmetric:
+            _refuse_under_grad("compute_polynomial(not_symmetric=True)", "the pure-phase filter is not differentiated")
+        _check_grad(img, kernel, "compute_polynomial")
+        return _apply_taps_function(img, kernel, taps, per_plane, _BOUNDARY[method], (alpha, b))
     if not_symmetric:
         _check_phase_sides(shape[2], shape[3])
     bnd = _BOUNDARY[method]
@@ -229,6 +374,8 @@ def inverse_filtering_nonsymmetric(img, kernel, alpha=2, b=4, correlate=False, r
     tensor, shape, dt = _check_image(img, allow_half=True)
     taps, per_plane = _check_kernel(kernel, "fft", shape, pad_domain=True, circular_only=bool(do_edgetaper),
                                     correlate=bool(correlate))
+    if _wants_grad(img, kernel):
+        _refuse_under_grad("inverse_filtering_nonsymmetric", "the pure-phase filter is not differentiated")
     pad = taps.shape[-1] // 2
     _check_phase_sides(shape[2] + 2 * pad, shape[3] + 2 * pad)
     extra = ()
