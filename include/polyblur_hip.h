@@ -362,6 +362,23 @@ int pb_convolve2d_taps_backward(pb_ctx *ctx, const float *x, const float *grad_o
 int pb_compute_polynomial_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps,
                                         int B, int C, int H, int W, const pb_taps *taps, float alpha, float beta, int boundary);
 
+/* ---- gradient of the blind estimation.  The README's promise covers the headline call too: in the reference the kernel that
+ * gaussian_blur_estimation returns (blur_estimation.py:18-79) is a differentiable function of the image -- through the tap formula
+ * (:189-232), sigma and rho (:171-185), the cubic interpolation (:138-148), the directional maxima (torch.amax: to the arg-max
+ * pixel, :122-134), the spectral derivative (filters.py:159-186) and the min / max normalisation (:96-109).
+ *
+ * pb_estimate_blur_backward: grad_in (B,C,H,W; written, not accumulated) = d loss / d in for the upstream gradients grad_kernel
+ * ((B, ker_size, ker_size), of the central taps of the records' kernels; or NULL) and grad_sigma_rho ((B, 2), of (sigma, rho); or
+ * NULL; not both NULL) -- all DEVICE memory.  dev_info: the B records pb_estimate_blur wrote for `in` with the same options; the
+ * direction (i_min, theta), the range (gray_min, gray_max) and the state of the clamps of sigma^2 / rho^2 are taken from them;
+ * the arg-max pixels are found again, and the magnitudes, sigma and rho are evaluated again at those pixels in double (the
+ * records' fp32 values carry the line transforms' rounding, which the chain amplifies).  fp32 images, opt->q == 0, odd
+ * ker_size up to 25 (0 means 25), no forced direction: PB_ERR_UNSUPPORTED otherwise, before any launch.  Scratch: three fp32 planes per image ("estg.gray", "estg.gx", "estg.gy") and the partials ("estg.part").  fp32 sums
+ * in a fixed order, no float atomics: the same call gives the same bits.  theta carries no gradient (it comes from integers).   */
+int pb_estimate_blur_backward(pb_ctx *ctx, const float *in, int B, int C, int H, int W, const pb_options *opt,
+                              const pb_blur_info *dev_info, const float *grad_kernel, const float *grad_sigma_rho,
+                              int ker_size, float *grad_in);
+
 /* The pure-phase polynomial takes the plane pairs of an image in groups whose complex scratch (one Hp x Wp float2 plane per
  * pair) stays within `bytes`; one pair is always allowed.  0 = the default, 256 MiB.  Results do not depend on it.       */
 int pb_set_phase_budget(pb_ctx *ctx, size_t bytes);

@@ -10,7 +10,10 @@ from .deblurring import polyblur_deblurring, polyblur_deblurring_uint8, Polyblur
 from .nonblind import inverse_filtering_rank3, convolve2d, edgetaper  # noqa: F401
 # ... and for kernels that are not point-symmetric: the pure-phase filter (reference deblurring.py:113-169, not_symmetric=True)
 from .nonblind import compute_polynomial, inverse_filtering_nonsymmetric  # noqa: F401
+# the blind estimation itself, differentiable (reference blur_estimation.py:18-79)
+from .estimation import gaussian_blur_estimation  # noqa: F401
 
 __all__ = ["polyblur_deblurring", "polyblur_deblurring_uint8", "PolyblurDeblurring",
-           "inverse_filtering_rank3", "convolve2d", "edgetaper", "compute_polynomial", "inverse_filtering_nonsymmetric"]
+           "inverse_filtering_rank3", "convolve2d", "edgetaper", "compute_polynomial", "inverse_filtering_nonsymmetric",
+           "gaussian_blur_estimation"]
 __version__ = "0.1.0"

@@ -163,6 +163,9 @@ def polyblur_deblurring(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, sigma_
         raise ValueError("expected a (B,C,H,W) tensor, got shape %r" % (tuple(img.shape),))
     if img.dtype not in (torch.float32, torch.float16):
         raise TypeError("tensor dtype must be float32 or float16 (the reference is float32-only)")
+    if torch.is_grad_enabled() and img.requires_grad:
+        return _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_interpolated_angles, remove_halo, edgetaping,
+                                 prefiltering, discard_saturation, multichannel_kernel, method, support, return_info, temporaries)
     _check_image_size(*img.shape[-2:])
     if temporaries == "fp16" and img.dtype != torch.float16:
         raise ValueError("temporaries='fp16' applies to float16 images only")
@@ -198,6 +201,48 @@ def polyblur_deblurring(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, sigma_
     if verbose:
         _print_stage_times(prof, time() - start)
     return (out, _info_to_dicts(info, n_angles, n_interpolated_angles)) if return_info else out
+
+
+def _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_interpolated_angles, remove_halo, edgetaping,
+                      prefiltering, discard_saturation, multichannel_kernel, method, support, return_info, temporaries):
+    """polyblur_deblurring of a tensor that requires grad (the reference's README: "fully differentiable"): the blind call as a
+    composition of the package's own differentiable functions -- estimate (estimation.py), non-blind step
+    (nonblind.py; 4.7), clip, n_iter times (deblurring.py:54-90).  Every refusal comes before any device work."""
+    import torch
+    from .estimation import gaussian_blur_estimation
+    from .nonblind import _refuse_under_grad, inverse_filtering_rank3
+    what = "polyblur_deblurring"
+    for flag, name, why in ((remove_halo, "remove_halo", "halo masking is not differentiated"),
+                            (edgetaping, "edgetaping", "the edgetaper is not differentiated"),
+                            (prefiltering, "prefiltering", "the edge-aware prefilters are not differentiated")):
+        if flag:
+            _refuse_under_grad("%s(%s=True)" % (what, name), why)
+    if q > 0:
+        _refuse_under_grad("%s(q=%g)" % (what, q), "the backward of torch.quantile is not built -- pass q=0, which is what the blind driver defaults to")
+    if method == "direct_separable":
+        _refuse_under_grad(what + "(method='direct_separable')", "the x-t separable approximation is not differentiated")
+    if method not in ("fft", "direct"):
+        raise ValueError("%s not implemented" % method)
+    if not (isinstance(ker_size, (int, np.integer)) and 3 <= ker_size <= capi.PB_KSIZE and ker_size % 2 == 1):
+        _refuse_under_grad("%s(ker_size=%r)" % (what, ker_size), "gradients are built for odd kernel sizes from 3 to 25")
+    if support != "full":
+        _refuse_under_grad("%s(support=%r)" % (what, support), "gradients are built for support='full'")
+    if temporaries != "fp32":
+        _refuse_under_grad("%s(temporaries=%r)" % (what, temporaries), "gradients are built for float32 images and temporaries")
+    if return_info:
+        _refuse_under_grad(what + "(return_info=True)", "the records are not part of the graph -- call gaussian_blur_estimation for the kernels")
+    if img.dtype == torch.float16:
+        _refuse_under_grad(what + " of a float16 image", "gradients are built for float32 images")
+    if not img.is_cuda:
+        _refuse_under_grad(what, "img requires grad and is a CPU tensor -- gradients are built for ROCm tensors only")
+    if not (isinstance(n_iter, (int, np.integer)) and n_iter >= 0):
+        raise ValueError("n_iter must be an integer >= 0")
+    x = img
+    for _ in range(int(n_iter)):
+        kernel = gaussian_blur_estimation(x, q=0, n_angles=n_angles, n_interpolated_angles=n_interpolated_angles, c=c, b=b,
+                                          ker_size=ker_size, discard_saturation=discard_saturation, multichannel=multichannel_kernel)
+        x = inverse_filtering_rank3(x, kernel, alpha, beta, method=method).clip(0, 1)
+    return x if n_iter > 0 else img.clone()
 
 
 def polyblur_deblurring_uint8(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, sigma_r=0.8, sigma_s=2.0, ker_size=25,
@@ -390,6 +435,12 @@ class PolyblurDeblurring(_Base):
                 q=0.0, n_angles=6, n_interpolated_angles=30, remove_halo=False, edgetaping=False, prefiltering=False,
                 discard_saturation=False, multichannel_kernel=False, method='fft', device=None, **extras):
         if self.patch_decomposition:
+            if _is_torch_tensor(images) and images.requires_grad:
+                import torch
+                if torch.is_grad_enabled():
+                    from .nonblind import _refuse_under_grad
+                    _refuse_under_grad("PolyblurDeblurring(patch_decomposition=True)", "the patch extraction and the windowed overlap-add "
+                                       "(pb_extract_patches, pb_overlap_add) are not differentiated")
             return _patchwise_deblurring(images, self.patch_size, self.patch_overlap, self.batch_size,
                                          dict(n_iter=n_iter, c=c, b=b, alpha=alpha, beta=beta, ker_size=ker_size,
                                               sigma_s=sigma_s, sigma_r=sigma_r, remove_halo=remove_halo,

@@ -334,6 +334,20 @@ class Engine:
         self._check(self.lib.pb_compute_polynomial_taps_backward(self.ctx, x_ptr, grad_out_ptr, grad_x_ptr, grad_taps_ptr, B, Cc, H, W,
                                                                  ks.handle, float(alpha), float(beta), int(boundary)))
 
+    # ---- the blind estimation on device pointers, and its backward pass --------------------------------------------------
+    def estimate_blur_ptr(self, in_ptr: int, dtype: int, shape, opts: capi.pb_options, info_ptr: int):
+        """B records into device memory at info_ptr (pb_estimate_blur); asynchronous on the context's stream"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_estimate_blur(self.ctx, in_ptr, int(dtype), B, Cc, H, W, C.byref(opts), info_ptr))
+
+    def estimate_blur_backward_ptr(self, in_ptr: int, shape, opts: capi.pb_options, info_ptr: int, grad_kernel_ptr, grad_sigma_rho_ptr,
+                                   ker_size: int, grad_in_ptr: int):
+        """d loss / d image for upstream gradients of the (B,k,k) kernels and / or of (sigma, rho) (B,2); either may be None
+        (pb_estimate_blur_backward: float32 images, q = 0, odd ker_size up to 25)"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_estimate_blur_backward(self.ctx, in_ptr, B, Cc, H, W, C.byref(opts), info_ptr, grad_kernel_ptr,
+                                                       grad_sigma_rho_ptr, int(ker_size), grad_in_ptr))
+
     def _taps_call(self, x: np.ndarray, call):
         x = np.ascontiguousarray(x)
         din = self.to_device("np.in", x)

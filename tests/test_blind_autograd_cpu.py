@@ -1,0 +1,216 @@
+"""The differentiable blind path, the part that needs no GPU:
+
+  * the closed form of the spectral derivative's impulse response against numpy.fft.ifft;
+  * tests/estimation_grad_ref.py -- the float64 restatement of the estimation's backward and of the chained blind gradient --
+    against the reference's own float32 autograd (tests/golden/blind_grad.npz, written by
+    tests/golden/make_golden_blind_autograd.py).  The bound is the reference's float32 error, so it is measured, not chosen --
+    largest |restatement - golden| / max |golden| per case:
+        e00 3.4e-7, e01 4.1e-7, e02 1.3e-6, e03 2.6e-7 (estimation alone, gradients up to 0.91),
+        b00 1.8e-6, b01 2.6e-6, b02 4.9e-6, b03 1.9e-6, b04 2.0e-6, b05 3.0e-6, b06 1.4e-5 (blind chains, gradients of 3.5 to 11.5),
+    er.BOUND_GOLDEN = 5.6e-5 = 4 x the largest of them; with every estimated kernel detached the same chains miss the goldens by
+    0.42 to 1.0 of max |golden|, more than 100 x that bound: the estimation's path is under test;
+  * the margins every committed case was searched for, recomputed here: arg-max runner-up, gray extrema, interpolated minimum,
+    the clamps of sigma^2 / rho^2, and the clamp of every iteration's output; at least two cases with (sigma, rho) unclamped and one
+    with rho clamped at 0.3, whose branch then passes exactly nothing;
+  * er.TOL_EST, the GPU test's tolerance for pb_estimate_blur_backward, is 4 x the error of the float32 CPU evaluation of the
+    restatement against float64 over the GPU test's cases (measured here: 2.30e-6 of max |grad|, the 130 x 257 case);
+  * what the constructed images of the GPU test are for holds: arg-max pixels in row 0, the last row and the last column; ties at
+    both ends of the range; the largest gradients under the saturation mask;
+  * every refusal under grad is raised before any device work."""
+import json
+
+import numpy as np
+import pytest
+import torch
+
+import autograd_ref as ar
+import estimation_grad_ref as er
+
+
+def golden_cases(golden, kind=None):
+    d = golden("blind_grad.npz")
+    return [(c, d[c["name"] + "_x"], d[c["name"] + "_w"], d[c["name"] + "_gx"]) for c in json.loads(str(d["cases"]))
+            if kind in (None, c["kind"])]
+
+
+@pytest.mark.parametrize("N", [2, 3, 4, 37, 40, 45, 48])
+def test_closed_form_of_the_spectral_derivative(N):
+    err = float(np.abs(er.deriv_kernel(N) - er.deriv_kernel_by_ifft(N)).max())
+    assert err < 1e-13, (N, err)
+    # ... and as the matrix the restatement applies: the derivative of a line the reference's way
+    x = np.random.default_rng(N).random(N)
+    U = np.fft.fftshift(np.fft.fft(x))
+    want = np.real(np.fft.ifft(np.fft.ifftshift(2 * np.pi * ((np.arange(N) - N // 2) / N) * (-U.imag + 1j * U.real))))
+    assert float(np.abs(er.deriv_matrix(N) @ x - want).max()) < 1e-13
+
+
+@pytest.fixture(scope="module")
+def against_goldens(golden):
+    """per committed case: (name, kind, relative error of the restatement, relative miss of the detached chain)"""
+    rows = []
+    for c, x, w, gx in golden_cases(golden):
+        scale = float(np.abs(gx).max())
+        if c["kind"] == "estimation":
+            g = er.estimate_backward(er.estimate(x), grad_kernel=w)
+            detached = np.zeros_like(g)                   # (a constant kernel passes nothing)
+        else:
+            _, steps = er.blind(x, c["n_iter"], c["alpha"], c["beta"], c["method"])
+            g = er.blind_gradient(x, w, c["n_iter"], c["alpha"], c["beta"], c["method"], steps=steps)
+            detached = er.blind_gradient(x, w, c["n_iter"], c["alpha"], c["beta"], c["method"], steps=steps, detach_kernel=True)
+        rows.append((c["name"], c["kind"], float(np.abs(g - gx).max()) / scale, float(np.abs(detached - gx).max()) / scale, scale))
+    return rows
+
+
+def test_restatement_against_the_references_float32_autograd(against_goldens):
+    for name, kind, err, miss, scale in against_goldens:
+        print("%s %-10s restatement %.3g, kernel detached %.3g of max |golden| = %.3g" % (name, kind, err, miss, scale))
+    worst = max(r[2] for r in against_goldens)
+    print("largest %.3g -> 4 x = %.3g; er.BOUND_GOLDEN = %.3g" % (worst, 4 * worst, er.BOUND_GOLDEN))
+    assert abs(4 * worst - er.BOUND_GOLDEN) <= 0.05 * er.BOUND_GOLDEN         # the constant IS 4 x this measurement (same file, same arithmetic)
+    for name, kind, err, miss, scale in against_goldens:
+        assert err <= er.BOUND_GOLDEN, (name, err)
+        assert miss > 100 * er.BOUND_GOLDEN, (name, miss)
+
+
+def test_margins_of_every_committed_case(golden):
+    unclamped = rho_low = 0
+    for c, x, w, gx in golden_cases(golden):
+        if c["kind"] == "estimation":
+            steps = [(x, er.estimate(x), None)]
+        else:
+            _, steps = er.blind(x, c["n_iter"], c["alpha"], c["beta"], c["method"])
+            assert len(steps) == c["n_iter"]
+        for it, (xi, recs, yu) in enumerate(steps):
+            m = er.margins(recs)
+            print(c["name"], it, "arg-max %.2g gray %.2g interp %.2g clamp %.2g" % m[:4], m[4], "" if yu is None else "output margin %.2g" % ar.clamp_margin(yu)[0])
+            assert m[0] >= 1e-3 and m[1] >= 1e-3 and m[2] >= 1e-3 and m[3] >= 1e-2, (c["name"], it, m)
+            assert yu is None or ar.clamp_margin(yu)[0] > 1e-3, (c["name"], it)
+            assert [list(f) for f in m[4]] == (c["clamped"] if yu is None else c["clamped"][it])
+        first = er.margins(steps[0][1])[4]
+        unclamped += all(f == (False, False) for f in first)
+        rho_low += all(f == (False, True) for f in first)
+        if all(f == (False, True) for f in first):
+            recs = steps[0][1]
+            assert all(abs(float(r["rho"]) - 0.3) < 1e-15 for r in recs)
+            up = np.zeros((len(recs), 2))
+            up[:, 1] = 1.0
+            assert not er.estimate_backward(recs, grad_sigma_rho=up).any()          # the clamped branch: exactly zero
+    assert unclamped >= 2 and rho_low >= 1
+
+
+@pytest.fixture(scope="module")
+def float32_errors(golden):
+    rows = []
+    todo = [(cid, x, sat, er.kernel_weights(5, x.shape[0])) for cid, x, sat in er.backward_cases()]
+    todo += [(c["name"], x, False, w) for c, x, w, _ in golden_cases(golden, "estimation")]
+    for cid, x, sat, w in todo:
+        g64 = er.estimate_backward(er.estimate(x, discard_saturation=sat), grad_kernel=w)
+        g32 = er.estimate_backward(er.estimate(x, discard_saturation=sat, dtype=np.float32), grad_kernel=w, dtype=np.float32)
+        assert g32.dtype == np.float32
+        rows.append((cid, er.per_image_error(g32, g64)))
+    return rows
+
+
+def test_backward_tolerance_is_four_times_the_fp32_cpu_error(float32_errors):
+    for cid, e in float32_errors:
+        print("%-12s fp32 vs float64: %.3g of max |grad|" % (cid, e))
+    worst = max(e for _, e in float32_errors)
+    print("largest %.3g -> 4 x = %.3g; er.TOL_EST = %.3g" % (worst, 4 * worst, er.TOL_EST))
+    # the constant was derived from this measurement; a re-measurement on another CPU sums in another order and must land within a
+    # factor 1.5 of it -- beyond that the constant is stale
+    assert er.TOL_EST / 1.5 <= 4 * worst <= er.TOL_EST * 1.5
+
+
+def test_constructed_images_do_what_they_are_for():
+    cases = {cid: (x, sat) for cid, x, sat in er.backward_cases()}
+    assert cases["130x257"][0].shape == (1, 1, 130, 257) and er.case_ok(er.estimate(cases["130x257"][0]))
+    x, _ = cases["edges"]
+    H, W = x.shape[-2:]
+    r = er.estimate(x)[0]
+    rows, cols = {int(a) // W for a in r["arg"]}, {int(a) % W for a in r["arg"]}
+    assert 0 in rows and H - 1 in rows and W - 1 in cols and er.margins([r])[0] >= 1e-3
+    x, _ = cases["ties"]
+    r = er.estimate(x)[0]
+    assert r["lo"] == 0.0 and r["hi"] == 1.0 and int((r["gray"] == 0.0).sum()) == 3 and int((r["gray"] == 1.0).sum()) == 4
+    assert er.margins([r])[0] >= 1e-3 and er.margins([r])[2] >= 1e-3
+    x, sat = cases["saturated"]
+    assert sat
+    masked, free = er.estimate(x, discard_saturation=True)[0], er.estimate(x)[0]
+    g = free["gray"].reshape(-1)
+    assert all(g[a] > er.SAT_THRESHOLD for a in free["arg"]) and not any(g[a] > er.SAT_THRESHOLD for a in masked["arg"])
+    assert er.margins([masked])[0] >= 1e-3 and er.margins([masked])[2] >= 1e-3
+
+
+# ---------------------------------------------------------------------------------------------
+# the public surface and its refusals: all before any device work
+# ---------------------------------------------------------------------------------------------
+def test_symbol_is_declared_and_bound():
+    import os
+    from polyblur_amd import _capi as capi
+    import polyblur_amd as pa
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "polyblur_hip.h")).read()
+    assert "int pb_estimate_blur_backward(" in header and "pb_estimate_blur_backward" in capi.SYMBOLS
+    assert "#define PB_VERSION 200" in header
+    assert "gaussian_blur_estimation" in pa.__all__ and callable(pa.gaussian_blur_estimation)
+
+
+@pytest.fixture
+def no_library(monkeypatch):
+    """any attempt to load the library or to make an engine is an error"""
+    from polyblur_amd import _capi as capi
+    import polyblur_amd.engine as engine
+
+    def boom(*a, **k):
+        raise AssertionError("device work before the refusal")
+    monkeypatch.setattr(capi, "load_library", boom)
+    for mod in ("polyblur_amd.engine", "polyblur_amd.estimation", "polyblur_amd.nonblind", "polyblur_amd.deblurring"):
+        monkeypatch.setattr(mod + ".get_engine", boom)
+    return engine
+
+
+def test_refusals_of_gaussian_blur_estimation(no_library):
+    import polyblur_amd as pa
+    x = torch.rand(1, 3, 16, 18, requires_grad=True)
+    with pytest.raises(NotImplementedError, match="has no backward pass.*CPU tensor"):
+        pa.gaussian_blur_estimation(x, q=0.0)
+    with pytest.raises(NotImplementedError, match="has no backward pass.*float32"):
+        pa.gaussian_blur_estimation(x.detach().half().requires_grad_(True), q=0.0)
+    with pytest.raises(NotImplementedError, match="q=0, which is what the blind driver defaults to"):
+        pa.gaussian_blur_estimation(x)                                            # (the function's own default is q = 1e-4)
+    for k in (24, 27):
+        with pytest.raises(NotImplementedError):
+            pa.gaussian_blur_estimation(x.detach(), ker_size=k)
+    with pytest.raises(NotImplementedError):
+        pa.gaussian_blur_estimation(torch.rand(1, 2, 16, 18), multichannel=True)
+    with pytest.raises(ValueError):
+        pa.gaussian_blur_estimation(x.detach(), thetas=torch.linspace(0, 180, 6))
+    with pytest.raises(ValueError):
+        pa.gaussian_blur_estimation(x.detach(), q=0.5)
+
+
+@pytest.mark.parametrize("kwargs,match", [
+    (dict(), "CPU tensor"), (dict(half=True), "float32"), (dict(q=1e-4), "q=0, which is what the blind driver defaults to"),
+    (dict(remove_halo=True), "halo"), (dict(edgetaping=True), "edgetaper"), (dict(prefiltering=True), "prefilter"),
+    (dict(ker_size=24), "odd kernel sizes"), (dict(ker_size=31), "odd kernel sizes"), (dict(method="direct_separable"), "separable"),
+    (dict(support="adaptive"), "support"), (dict(return_info=True), "records"),
+])
+def test_refusals_of_the_blind_call_under_grad(no_library, kwargs, match):
+    import polyblur_amd as pa
+    kwargs = dict(kwargs)
+    x = torch.rand(1, 3, 16, 18)
+    if kwargs.pop("half", False):
+        x = x.half()
+    x.requires_grad_(True)
+    with pytest.raises(NotImplementedError, match="has no backward pass.*" + match):
+        pa.polyblur_deblurring(x, **kwargs)
+    with pytest.raises(NotImplementedError, match="has no backward pass.*" + match):
+        pa.PolyblurDeblurring()(x, **kwargs)
+
+
+def test_refusals_that_remain(no_library):
+    import polyblur_amd as pa
+    x = torch.rand(1, 3, 16, 18, requires_grad=True)
+    with pytest.raises(NotImplementedError, match="has no backward pass.*temporaries"):
+        pa.polyblur_deblurring(x.detach().half().requires_grad_(True), temporaries="fp16")
+    with pytest.raises(NotImplementedError, match="has no backward pass.*overlap-add"):
+        pa.PolyblurDeblurring(patch_decomposition=True, patch_size=8)(x)
