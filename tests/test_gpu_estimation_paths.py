@@ -141,7 +141,8 @@ def test_half_gradient_planes_of_an_fp16_call(engines, runtime_plan_engine):
     image as fp16 planes where the compiled-plan line transforms can write them (csrc/filters.hip: halo_kernel's TG) -- z = M /
     (nM + M) is ~1e-5 on an image, so the fp16 rounding of its factors is far below the fp16 output's own rounding.  Against
     the same call with fp32 planes (a context whose column transforms are the run-time-plan kernels: no typed outputs) and
-    against the oracle on the fp16-rounded input (deblurring.py:193-208), at the fp16 tolerance of every other test."""
+    against the oracle on the fp16-rounded input (deblurring.py:193-208), at the fp16 tolerance of every other test.
+    (The mask's whole effect is below that tolerance here; the checks of its arithmetic that have power: tests/test_gpu_halo.py.)"""
     x, _ = synthetic_blurry_batch(2, 3, 1080, 1920, seed0=47)
     x16 = x.astype(np.float16)
     kw = dict(n_iter=2, c=0.362, b=0.468, alpha=6.0, beta=1.0, remove_halo=True)
