@@ -259,3 +259,24 @@ def test_large_kernel_sizes_with_edgetaping(golden, k, method):
     for i in range(2):
         out = ref.polyblur_deblurring(xs[i], n_iter=1, **kw)
         assert np.max(np.abs(out - xs[i + 1])) < 1e-5, (k, method, i)
+
+
+def test_estimation_of_other_direction_counts(golden):
+    """estimate_gaussian_blur with n_angles in {1, 2, 3, 5, 7, 12} x n_interpolated_angles in {7, 30, 64}, q in {0, 1e-4, 0.02}, with and
+    without the saturation mask, against the reference on planted inputs (tests/golden/make_golden_estimation.py; the grids
+    truncated to whole degrees as deblurring.py:62-63 builds them) -- theta exactly, sigma / rho / kernel at the bounds of
+    tests/test_gpu_parity.py::test_estimate_blur"""
+    g = golden("estimation_planted.npz")
+    names = sorted(k[:-2] for k in g.files if k.endswith("_x"))
+    assert len(names) == 21 and {tuple(g[n + "_opts"][:2].astype(int)) for n in names} >= {(a, i) for a in (1, 2, 3, 5, 7, 12) for i in (7, 30, 64)}
+    for n in names:
+        x = g[n + "_x"]
+        x = x.astype(np.float32) * np.float32(1.0 / 255.0) if x.dtype == np.uint8 else x
+        na, ni, q, sat, c, b = g[n + "_opts"]
+        k, info = ref.estimate_gaussian_blur(x, c=c, b=b, q=q, n_angles=int(na), n_interpolated_angles=int(ni),
+                                             discard_saturation=bool(sat), return_info=True)
+        assert np.array_equal(info["theta"], g[n + "_theta"]), n
+        assert maxabs(info["sigma"], g[n + "_sigma"]) < 2e-5 and maxabs(info["rho"], g[n + "_rho"]) < 2e-5, n
+        assert maxabs(k, g[n + "_kernel"]) < 1e-5, n
+    # the mask changes the answer on the saturated entry
+    assert abs(float(g["saturated_0_sigma"][0]) - float(g["saturated_1_sigma"][0])) > 0.05
