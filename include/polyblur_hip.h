@@ -387,6 +387,27 @@ int pb_set_phase_budget(pb_ctx *ctx, size_t bytes);
 int pb_halo_mask(pb_ctx *ctx, const float *x, const float *y, const float *grad0_x,
                  const float *grad0_y, float *out, int B, int C, int H, int W);
 
+/* ---- gradient of halo masking (remove_halo=True under autograd).
+ * pb_fourier_gradients_backward: the backward of pb_fourier_gradients (filters.fourier_gradients, filters.py:159-186).  The
+ * circulant of the spectral derivative is odd, so its transpose is its negative: grad_planes (P planes of H x W; written, not
+ * accumulated) = -(Dx grad_gx + Dy grad_gy).  Either upstream gradient may be NULL, not both; grad_planes may alias neither.
+ * Scratch: one plane set ("halog.fy") when both are given.                                                                  */
+int pb_fourier_gradients_backward(pb_ctx *ctx, const float *grad_gx, const float *grad_gy, int P, int H, int W,
+                                  float *grad_planes);
+
+/* pb_halo_mask_backward: the backward of pb_halo_mask (deblurring.halo_masking, deblurring.py:173-208, bug-compatible: M uses
+ * grad_y * grad_y, :174; torch.clamp(min=0), :184, passes the gradient where M / (nM + M) >= 0).  grad_out is the upstream
+ * gradient of out; grad_x, grad_y, grad_grad0_x, grad_grad0_y are d loss / d x, y, grad0_x, grad0_y.  Any of the four outputs may
+ * be NULL (not all), and what a NULL output makes unnecessary is not computed; all (B,C,H,W) float32 DEVICE memory, written, not
+ * accumulated; no output may alias an input or another output.  nM and the x-derivative of y are formed again by the forward's
+ * launchers and M, z are evaluated as the forward evaluates them: a sample is on the side of the clamp the forward put it on.
+ * Scratch: two plane sets ("halog.ox", and "halog.t" with grad_y), P floats of nM ("halog.nM") and, with a grad0 output, P of S
+ * and the partial sums ("halog.S", "halog.part").  fp32 sums in a fixed order, no float atomics: the same call gives the same
+ * bits.  Widths that pb_fft_length_supported rejects: PB_ERR_UNSUPPORTED before any launch.                                  */
+int pb_halo_mask_backward(pb_ctx *ctx, const float *x, const float *y, const float *grad0_x, const float *grad0_y,
+                          const float *grad_out, float *grad_x, float *grad_y, float *grad_grad0_x, float *grad_grad0_y,
+                          int B, int C, int H, int W);
+
 /* domain_transform.recursive_filter (domain_transform.py:6-63; native twin RF.cpp:43-92).
  * joint may be NULL (filter guided by itself).                                           */
 int pb_dt_recursive_filter(pb_ctx *ctx, const void *in, const void *joint, void *out, int dtype,

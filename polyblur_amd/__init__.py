@@ -12,8 +12,10 @@ from .nonblind import inverse_filtering_rank3, convolve2d, edgetaper  # noqa: F4
 from .nonblind import compute_polynomial, inverse_filtering_nonsymmetric  # noqa: F401
 # the blind estimation itself, differentiable (reference blur_estimation.py:18-79)
 from .estimation import gaussian_blur_estimation  # noqa: F401
+# halo masking and the spectral derivative, differentiable (reference deblurring.py:193-208, filters.py:159-186)
+from .halo import fourier_gradients, halo_masking  # noqa: F401
 
 __all__ = ["polyblur_deblurring", "polyblur_deblurring_uint8", "PolyblurDeblurring",
            "inverse_filtering_rank3", "convolve2d", "edgetaper", "compute_polynomial", "inverse_filtering_nonsymmetric",
-           "gaussian_blur_estimation"]
+           "gaussian_blur_estimation", "fourier_gradients", "halo_masking"]
 __version__ = "0.1.0"

@@ -10,6 +10,9 @@
 
 // (g_dtype: the type of the gradient planes gx, gy, ox -- PB_F32, or PB_F16 inside an fp16 call of the pipeline)
 int pb_grad_energy(pb_ctx *ctx, const void *gx, const void *gy, float *nM, int P, long HW, int g_dtype = PB_F32);
+int pb_fourier_gradients_backward_impl(pb_ctx *ctx, const float *grad_gx, const float *grad_gy, int P, int H, int W, float *grad_planes);   // halo_grad.hip
+int pb_halo_mask_backward_impl(pb_ctx *ctx, const float *x, const float *y, const float *grad0_x, const float *grad0_y, const float *grad_out,
+                               float *grad_x, float *grad_y, float *grad_grad0_x, float *grad_grad0_y, int B, int C, int H, int W);
 int pb_halo_apply(pb_ctx *ctx, const void *x, int x_dtype, int x_pitch, long x_plane, const float *y, const void *gx,
                   const void *gy, const void *ox, const float *nM, void *out, int out_dtype, int P, int H, int W,
                   int clamp01, const void *recomb_cur = nullptr, int recomb_cur_dtype = 0, const float *recomb_smooth = nullptr,
@@ -737,6 +740,21 @@ int pb_halo_mask(pb_ctx *ctx, const float *x, const float *y, const float *grad0
     rc = pb_fourier_gradients_impl(ctx, y, g.P, H, W, ox, nullptr);
     if (rc) return rc;
     return pb_halo_apply(ctx, x, PB_F32, W, g.HW, y, grad0_x, grad0_y, ox, nM, out, PB_F32, g.P, H, W, 0);
+}
+
+int pb_fourier_gradients_backward(pb_ctx *ctx, const float *grad_gx, const float *grad_gy, int P, int H, int W,
+                                  float *grad_planes) {
+    if (!ctx) return PB_ERR_BADARG;
+    PB_HIP(hipSetDevice(ctx->device));
+    return pb_fourier_gradients_backward_impl(ctx, grad_gx, grad_gy, P, H, W, grad_planes);
+}
+
+int pb_halo_mask_backward(pb_ctx *ctx, const float *x, const float *y, const float *grad0_x, const float *grad0_y,
+                          const float *grad_out, float *grad_x, float *grad_y, float *grad_grad0_x, float *grad_grad0_y,
+                          int B, int C, int H, int W) {
+    if (!ctx) return PB_ERR_BADARG;
+    PB_HIP(hipSetDevice(ctx->device));
+    return pb_halo_mask_backward_impl(ctx, x, y, grad0_x, grad0_y, grad_out, grad_x, grad_y, grad_grad0_x, grad_grad0_y, B, C, H, W);
 }
 
 int pb_dt_recursive_filter(pb_ctx *ctx, const void *in, const void *joint, void *out, int dtype, int B, int C, int H,

@@ -207,13 +207,15 @@ def _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_i
                       prefiltering, discard_saturation, multichannel_kernel, method, support, return_info, temporaries):
     """polyblur_deblurring of a tensor that requires grad (the reference's README: "fully differentiable"): the blind call as a
     composition of the package's own differentiable functions -- estimate (estimation.py), non-blind step
-    (nonblind.py; 4.7), clip, n_iter times (deblurring.py:54-90).  Every refusal comes before any device work."""
+    (nonblind.py; 4.7) with the halo mask where asked (halo.py; 4.9), clip, n_iter times (deblurring.py:54-90).  Every refusal
+    comes before any device work."""
     import torch
     from .estimation import gaussian_blur_estimation
     from .nonblind import _refuse_under_grad, inverse_filtering_rank3
     what = "polyblur_deblurring"
-    for flag, name, why in ((remove_halo, "remove_halo", "halo masking is not differentiated"),
-                            (edgetaping, "edgetaping", "the edgetaper is not differentiated"),
+    if remove_halo and not (img.is_cuda and img.dtype == torch.float32):     # (the stage's device check first: its reason names the stage)
+        _refuse_under_grad(what + "(remove_halo=True)", "halo masking is differentiated for float32 ROCm tensors only")
+    for flag, name, why in ((edgetaping, "edgetaping", "the edgetaper is not differentiated"),
                             (prefiltering, "prefiltering", "the edge-aware prefilters are not differentiated")):
         if flag:
             _refuse_under_grad("%s(%s=True)" % (what, name), why)
@@ -238,10 +240,14 @@ def _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_i
     if not (isinstance(n_iter, (int, np.integer)) and n_iter >= 0):
         raise ValueError("n_iter must be an integer >= 0")
     x = img
+    grad_img = None
+    if remove_halo and n_iter > 0:                           # of the original input, for every iteration (deblurring.py:61,83)
+        from .halo import fourier_gradients
+        grad_img = fourier_gradients(img)
     for _ in range(int(n_iter)):
         kernel = gaussian_blur_estimation(x, q=0, n_angles=n_angles, n_interpolated_angles=n_interpolated_angles, c=c, b=b,
                                           ker_size=ker_size, discard_saturation=discard_saturation, multichannel=multichannel_kernel)
-        x = inverse_filtering_rank3(x, kernel, alpha, beta, method=method).clip(0, 1)
+        x = inverse_filtering_rank3(x, kernel, alpha, beta, remove_halo=bool(remove_halo), grad_img=grad_img, method=method).clip(0, 1)
     return x if n_iter > 0 else img.clone()
 
 

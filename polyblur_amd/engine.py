@@ -400,6 +400,29 @@ class Engine:
         self.synchronize()
         return dout.download(x.shape, np.float32)
 
+    # ---- halo masking and the spectral derivative on device pointers, and their backward passes ----------
+    def fourier_gradients_ptr(self, in_ptr: int, shape, gx_ptr, gy_ptr):
+        """gx / gy (either may be None) of the float32 planes at in_ptr (pb_fourier_gradients); asynchronous"""
+        H, W = (int(v) for v in shape[-2:])
+        self._check(self.lib.pb_fourier_gradients(self.ctx, in_ptr, int(np.prod(shape[:-2], dtype=np.int64)), H, W, gx_ptr, gy_ptr))
+
+    def fourier_gradients_backward_ptr(self, grad_gx_ptr, grad_gy_ptr, shape, grad_in_ptr: int):
+        """grad_in = -(Dx grad_gx + Dy grad_gy); either upstream may be None, not both (pb_fourier_gradients_backward)"""
+        H, W = (int(v) for v in shape[-2:])
+        self._check(self.lib.pb_fourier_gradients_backward(self.ctx, grad_gx_ptr, grad_gy_ptr, int(np.prod(shape[:-2], dtype=np.int64)),
+                                                           H, W, grad_in_ptr))
+
+    def halo_mask_ptr(self, x_ptr: int, y_ptr: int, g0x_ptr: int, g0y_ptr: int, out_ptr: int, shape):
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_halo_mask(self.ctx, x_ptr, y_ptr, g0x_ptr, g0y_ptr, out_ptr, B, Cc, H, W))
+
+    def halo_mask_backward_ptr(self, x_ptr: int, y_ptr: int, g0x_ptr: int, g0y_ptr: int, grad_out_ptr: int, grad_x_ptr, grad_y_ptr,
+                               grad_g0x_ptr, grad_g0y_ptr, shape):
+        """any of the four outputs may be None, not all (pb_halo_mask_backward)"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_halo_mask_backward(self.ctx, x_ptr, y_ptr, g0x_ptr, g0y_ptr, grad_out_ptr, grad_x_ptr, grad_y_ptr,
+                                                   grad_g0x_ptr, grad_g0y_ptr, B, Cc, H, W))
+
     def dt_recursive_filter(self, x: np.ndarray, sigma_s=60.0, sigma_r=0.4, num_iterations=3, joint=None) -> np.ndarray:
         x = np.ascontiguousarray(x)
         B, Cc, H, W = x.shape

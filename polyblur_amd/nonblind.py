@@ -30,8 +30,9 @@ Gradients (the reference's README: "fully differentiable"): ``convolve2d``, ``co
 that requires grad -- with respect to the image and to the taps (not to alpha and b; no double backward).  The backward passes
 are the engine's too (pb_convolve2d_taps_backward, pb_compute_polynomial_taps_backward); the pad, crop and clamp of
 ``inverse_filtering_rank3`` are then torch's own ops -- the replicate pad composed of slices, expand and cat, whose backward is
-an ordered sum where F.pad's adds with float atomics.  Under grad: float32 ROCm tensors and odd kernel sides only, and no
-``remove_halo``, ``do_edgetaper``, ``edgetaper()``, ``not_symmetric`` or ``inverse_filtering_nonsymmetric``
+an ordered sum where F.pad's adds with float atomics.  ``remove_halo=True`` under grad is ``halo_masking`` (halo.py; DESIGN.md
+4.9) between the crop and the clamp, differentiable with respect to ``grad_img`` too.  Under grad: float32 ROCm tensors and odd
+kernel sides only, and no ``do_edgetaper``, ``edgetaper()``, ``not_symmetric`` or ``inverse_filtering_nonsymmetric``
 (NotImplementedError before any device work).  Without grad nothing changes: the calls below run as before.
 
 The arithmetic is the HIP engine's (include/polyblur_hip.h: pb_taps_create and the *_taps calls); nothing runs on the CPU.
@@ -304,18 +305,32 @@ def inverse_filtering_rank3(img, kernel, alpha=2, b=4, correlate=False, remove_h
     tensor, shape, dt = _check_image(img, allow_half=True)
     taps, per_plane = _check_kernel(kernel, method, shape, pad_domain=True, circular_only=bool(do_edgetaper),
                                     correlate=bool(correlate))
-    if _wants_grad(img, kernel):
+    halo_planes = tuple(grad_img) if remove_halo and isinstance(grad_img, (tuple, list)) and len(grad_img) == 2 else ()
+    if _wants_grad(img, kernel) or (halo_planes and _wants_grad(*halo_planes)):
         if remove_halo:
-            _refuse_under_grad("inverse_filtering_rank3(remove_halo=True)", "halo masking is not differentiated")
+            # (the stage's device check first: its reason names the stage)
+            import torch
+            for t in (img,) + halo_planes:                    # (the kernel's own checks follow: _check_grad)
+                if not _is_torch_tensor(t) or not t.is_cuda or t.dtype != torch.float32:
+                    _refuse_under_grad("inverse_filtering_rank3(remove_halo=True)", "halo masking is differentiated for float32 ROCm tensors only")
         if do_edgetaper:
             _refuse_under_grad("inverse_filtering_rank3(do_edgetaper=True)", "the edgetaper is not differentiated")
         _check_grad(img, kernel, "inverse_filtering_rank3")
-        # pad, crop and clamp are torch's own ops with torch's own backward; the polynomial is the engine's
+        # pad, crop and clamp are torch's own ops with torch's own backward; the polynomial and the mask are the engine's
         import torch
+        if remove_halo:
+            from .halo import _check_grad_img
+            _check_image_size(*shape[-2:])
+            if grad_img is not None:
+                _check_grad_img(grad_img, shape)
         pad = taps.shape[-1] // 2
         xp = _replicate_pad(img, pad)
         y = _apply_taps_function(xp, kernel, taps, per_plane, _BOUNDARY[method], (alpha, b), bool(correlate))
-        return torch.clamp(y[..., pad:-pad, pad:-pad], 0.0, 1.0)
+        y = y[..., pad:-pad, pad:-pad]
+        if remove_halo:
+            from .halo import halo_masking
+            y = halo_masking(img, y, grad_img)                # (grad_img None: fourier_gradients(img), inside the graph)
+        return torch.clamp(y, 0.0, 1.0)
     extra = ()
     if remove_halo:
         _check_image_size(*shape[-2:])
