@@ -1,0 +1,151 @@
+"""The package's autograd.Functions: the forward and backward passes are the engine's, on ROCm float32
+tensors and torch's current stream; no double backward.  The public functions import this module on first use under grad --
+it is the only one that needs torch at import time -- after every check and refusal of theirs has passed."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _capi as capi
+from ._frontend import bound_engine, staged
+
+
+def _upstream(g):
+    return g.detach().to(torch.float32).contiguous()
+
+
+def replicate_pad(x, pad):
+    """F.pad(x, (pad,) * 4, mode='replicate') -- the same values, bit for bit -- composed of slices, expand and cat: the backward
+    of torch's own replicate pad adds the pad's gradients into the edge pixels with float atomics on the GPU, so two identical
+    backward calls differ in the last bits; the backward of expand is an ordered sum"""
+    B, C, H, W = x.shape
+    x = torch.cat([x[:, :, :1].expand(B, C, pad, W), x, x[:, :, -1:].expand(B, C, pad, W)], dim=2)
+    return torch.cat([x[..., :1].expand(B, C, H + 2 * pad, pad), x, x[..., -1:].expand(B, C, H + 2 * pad, pad)], dim=3)
+
+
+class TapsFunction(torch.autograd.Function):
+    """convolve2d (poly is None) or compute_polynomial (poly = (alpha, b)) of a ROCm float32 image that is the whole
+    domain.  taps, eshape: the (B', kh, kw) host array and the engine's view of the image's shape that nonblind._check_kernel made of
+    `kernel` (already rotated when `correlate`);
+    kernel: the tensor itself, for the graph, or None when it is an array; call: the forward's engine call, the caller's own
+    (staged's form)."""
+
+    @staticmethod
+    def forward(ctx, img, kernel, taps, eshape, bnd, poly, correlate, call):
+        x = img.detach()
+        (out,), _ = staged(x, np.float32, call, taps=taps)
+        ctx.save_for_backward(x)
+        ctx.pb = (taps, bnd, poly, bool(correlate), int(img.shape[0]), eshape)
+        # (of the kernel only what the backward needs to shape its gradient: the tensor itself is not kept alive)
+        ctx.kernel_like = None if kernel is None else (tuple(int(v) for v in kernel.shape), kernel.dtype, kernel.device)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        (x,) = ctx.saved_tensors
+        taps, bnd, poly, correlate, B, eshape = ctx.pb
+        want_x, want_k = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        xin = x.contiguous()
+        g = _upstream(grad_out)
+        gx = torch.empty_like(xin) if want_x else None
+        gk = torch.empty(taps.shape, dtype=torch.float32, device=x.device) if want_k else None
+        with bound_engine(x) as eng:
+            ks = eng.set_taps(taps)
+            try:
+                args = (xin.data_ptr(), g.data_ptr(), gx.data_ptr() if want_x else None, gk.data_ptr() if want_k else None, eshape, ks)
+                if poly is None:
+                    eng.convolve2d_taps_backward_ptr(*args, bnd)
+                else:
+                    eng.compute_polynomial_taps_backward_ptr(*args, poly[0], poly[1], bnd)
+            finally:
+                ks.free()                               # (waits for the stream)
+        if want_k:
+            # back to kernel.shape: the taps were broadcast over the batch (summed here; the engine has summed over the
+            # planes of a one-channel kernel) and rotated for correlate=True (rotated back)
+            (kb, kc, kh, kw), kdtype, kdevice = ctx.kernel_like
+            gk = gk.view(B, kc, kh, kw)
+            if kb == 1 and B > 1:
+                gk = gk.sum(0, keepdim=True)
+            if correlate:
+                gk = gk.flip(-2, -1)
+            gk = gk.to(device=kdevice, dtype=kdtype)
+        return gx, gk, None, None, None, None, None, None
+
+
+class EstimationFunction(torch.autograd.Function):
+    """gaussian_blur_estimation of a ROCm float32 image with q = 0; the records stay on the device for the backward.
+    records: image -> its records; unpack: records -> the function's outputs (estimation._records, _kernel_of / _params_of)."""
+
+    @staticmethod
+    def forward(ctx, img, opts, ker_size, filters, records, unpack):
+        x = img.detach().contiguous()
+        rec = records(x)
+        ctx.save_for_backward(x, rec)
+        ctx.pb = (opts, int(ker_size), bool(filters))
+        out = unpack(rec)
+        if not filters:
+            ctx.mark_non_differentiable(out[2])               # (theta comes from integer tensors: blur_estimation.py:160-167)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        x, rec = ctx.saved_tensors
+        opts, ker_size, filters = ctx.pb
+        gk = gsr = None
+        if filters:
+            gk = _upstream(grads[0])
+        else:
+            gsr = torch.cat([grads[0].detach().to(torch.float32).reshape(-1, 1), grads[1].detach().to(torch.float32).reshape(-1, 1)], dim=1).contiguous()
+        gin = torch.empty_like(x)
+        with bound_engine(x) as eng:
+            eng.estimate_blur_backward_ptr(x.data_ptr(), x.shape, opts, rec.data_ptr(), gk.data_ptr() if filters else None,
+                                           None if filters else gsr.data_ptr(), ker_size if filters else capi.PB_KSIZE, gin.data_ptr())
+        return gin, None, None, None, None, None
+
+
+class FourierGradientsFunction(torch.autograd.Function):
+    """fourier_gradients of a ROCm float32 tensor: linear, nothing is saved.  gradients: image -> (gx, gy) (halo._gradients)"""
+
+    @staticmethod
+    def forward(ctx, img, gradients):
+        gx, gy = gradients(img.detach())
+        ctx.set_materialize_grads(False)                  # (an output the loss does not reach: None, and no transform for it)
+        return gx, gy
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, ggx, ggy):
+        if ggx is None and ggy is None:
+            return None, None
+        ggx, ggy = (None if g is None else _upstream(g) for g in (ggx, ggy))
+        like = ggx if ggx is not None else ggy
+        gin = torch.empty_like(like)
+        with bound_engine(like) as eng:
+            eng.fourier_gradients_backward_ptr(None if ggx is None else ggx.data_ptr(), None if ggy is None else ggy.data_ptr(),
+                                               like.shape, gin.data_ptr())
+        return gin, None
+
+
+class HaloMaskingFunction(torch.autograd.Function):
+    """halo_masking of ROCm float32 tensors with given gradient planes.  mask: (img, imout, gx, gy) -> the masked image (halo._mask)"""
+
+    @staticmethod
+    def forward(ctx, img, imout, gx, gy, mask):
+        x, y, a, b = (t.detach().contiguous() for t in (img, imout, gx, gy))
+        out = mask(x, y, a, b)
+        ctx.save_for_backward(x, y, a, b)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, y, a, b = ctx.saved_tensors
+        g = _upstream(grad_out)
+        outs = [torch.empty_like(x) if need else None for need in ctx.needs_input_grad[:4]]
+        with bound_engine(x) as eng:
+            eng.halo_mask_backward_ptr(x.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), g.data_ptr(),
+                                       *[o.data_ptr() if o is not None else None for o in outs], x.shape)
+        return tuple(outs) + (None,)

@@ -31,66 +31,11 @@ from time import time
 import numpy as np
 
 from . import _capi as capi
-from .engine import get_engine
-
-# 'direct_separable': the reference's own separable path raises NameError (blur_estimation.py:77, filters.py:71,78); its
-# intent -- a 1-D pass followed by an oblique 1-D pass with linear interpolation, separable_gaussian2d.cpp:91-183 -- is an
-# opt-in APPROXIMATION of the 25x25 kernel here (zero boundary like 'direct'); rank-1 kernels are exact either way
-_METHODS = {"fft": capi.PB_WRAP, "direct": capi.PB_ZERO, "direct_separable": capi.PB_ZERO}
-_SUPPORT = {"full": capi.PB_SUPPORT_FULL, "adaptive": capi.PB_SUPPORT_ADAPTIVE}
-_PREFILTER = {"bilateral": capi.PB_PREFILTER_BILATERAL, "domain_transform": capi.PB_PREFILTER_DOMAIN_TRANSFORM,
-              "normalized_convolution": capi.PB_PREFILTER_NORMALIZED_CONVOLUTION}
-
-
-def _check_image_size(h, w):
-    """Line lengths the spectral derivative takes (include/polyblur_hip.h: pb_fft_length_supported): whole lines in LDS up
-    to 20480 samples (8192 when a prime factor exceeds 7), through a line buffer in device memory up to 65536."""
-    lib = capi.load_library()
-    for n, what in ((int(h), "height"), (int(w), "width")):
-        if n >= 2 and not lib.pb_fft_length_supported(n):
-            raise ValueError("image %s %d is beyond the engine's spectral derivative: sides up to 65536 are supported" % (what, n))
-
-
-def _is_torch_tensor(x) -> bool:
-    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
-
-
-def _build_options(C, n_iter, c, b, alpha, beta, sigma_r, sigma_s, ker_size, q, n_angles, n_interpolated_angles,
-                   remove_halo, edgetaping, prefiltering, discard_saturation, multichannel_kernel, method, support,
-                   prefilter, force_theta_deg=-1.0, temporaries="fp32"):
-    if method == "direct_separable" and edgetaping:
-        raise NotImplementedError("edgetaping is not defined for method='direct_separable'")
-    if method not in _METHODS:
-        raise ValueError("%s not implemented" % method)          # reference: deblurring.py:119 (never raised there)
-    if temporaries not in ("fp32", "fp16"):
-        raise ValueError("temporaries must be 'fp32' or 'fp16'")
-    if support not in _SUPPORT:
-        raise ValueError("support must be 'full' or 'adaptive'")
-    if prefilter not in _PREFILTER:
-        raise ValueError("prefilter must be 'bilateral', 'domain_transform' or 'normalized_convolution'")
-    if not (isinstance(ker_size, (int, np.integer)) and 2 <= ker_size <= capi.PB_KSIZE_MAX):
-        # up to 25 the kernel lives in a 25 x 25 record; 26 .. 49 take the large-kernel pass (csrc/conv_big.hip); the replicate
-        # pad is ker_size // 2 (even sizes: off-centre, as the reference's grid arange(k) - (k - 1) // 2 and its two convolution
-        # paths place them).  sigma is clamped to 4, so 49 holds +-6 sigma: nothing beyond it is built
-        raise NotImplementedError("ker_size must be between 2 and 49")
-    if ker_size % 2 == 0 and method == "direct_separable":
-        raise NotImplementedError("an even ker_size is built for the 'fft' / 'direct' methods only (not with 'direct_separable')")
-    if ker_size > capi.PB_KSIZE and method == "direct_separable":
-        raise NotImplementedError("a ker_size above 25 is built for the 'fft' / 'direct' methods only (not with 'direct_separable')")
-    if not (0 <= q < 0.5):
-        raise ValueError("q must be in [0, 0.5)")
-    if multichannel_kernel and C not in (1, 3):
-        raise NotImplementedError("per-channel kernels crash in the reference for C not in {1,3}")
-    if not (1 <= n_angles <= capi.PB_MAX_ANGLES - 1 and 1 <= n_interpolated_angles <= capi.PB_MAX_INTERP):
-        raise ValueError("n_angles / n_interpolated_angles out of range")
-    from .engine import Engine
-    return Engine.make_options(n_iter=n_iter, c=c, b=b, alpha=alpha, beta=beta, sigma_r=sigma_r, sigma_s=sigma_s, q=q,
-                               n_angles=n_angles, n_interpolated_angles=n_interpolated_angles, remove_halo=remove_halo,
-                               edgetaping=edgetaping,
-                               prefilter=_PREFILTER[prefilter] if prefiltering else capi.PB_PREFILTER_NONE,
-                               discard_saturation=discard_saturation, boundary=_METHODS[method],
-                               support=_SUPPORT[support], force_theta_deg=force_theta_deg, ker_size=ker_size,
-                               separable_approx=(method == "direct_separable"), half_temporaries=(temporaries == "fp16"))
+from ._frontend import (CPU_WITH_GRAD, DTYPES, FLOAT32_ONLY, HALO_ONLY, NO_EDGETAPER, NO_QUANTILE, bound_engine, build_options,
+                        check_image_size, is_tensor, refuse_under_grad, staged, wants_grad)
+from .estimation import gaussian_blur_estimation
+from .halo import fourier_gradients
+from .nonblind import inverse_filtering_rank3
 
 
 def _info_to_dicts(info, n_angles, n_interp):
@@ -120,13 +65,29 @@ def _print_stage_times(prof, wall):
     print('-- polyblur (hip):    %1.5f s wall' % wall)
 
 
+def _run(x, dt, opts, return_info, device, verbose=False):
+    """the blind call on a (B,C,H,W) image of any kind (staged), of NumPy dtype dt -> (output, records or None, stage times or None)"""
+    def call(eng, i, o, ex):
+        if not verbose:
+            return eng.polyblur_ptr(i, o[0], DTYPES[np.dtype(dt)], x.shape, opts, want_info=return_info), None
+        eng.profile_begin()
+        try:
+            info = eng.polyblur_ptr(i, o[0], DTYPES[np.dtype(dt)], x.shape, opts, want_info=return_info)
+        finally:                                            # (a failed call must not leave the thread's context profiling)
+            prof = eng.profile_end()
+        return info, prof
+    (out,), (info, prof) = staged(x, dt, call, device=device)
+    return out, info, prof
+
+
 def polyblur_deblurring(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, sigma_r=0.8, sigma_s=2.0, ker_size=25, q=0.0,
                         n_angles=6, n_interpolated_angles=30, remove_halo=False, edgetaping=False, prefiltering=False,
                         discard_saturation=False, multichannel_kernel=False, method='fft', verbose=False, *,
                         support='full', prefilter='bilateral', return_info=False, device=None, temporaries='fp32'):
     """Blind deblurring of ``img`` -- see the module docstring; reference deblurring.py:23-96."""
     start = time()
-    if isinstance(img, np.ndarray):
+    array = isinstance(img, np.ndarray)
+    if array:
         # utils.to_tensor + unsqueeze (deblurring.py:46-48): HWC -> (1,C,H,W) float32 copy
         if img.ndim == 2:
             x = img[None, None]
@@ -135,71 +96,33 @@ def polyblur_deblurring(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, sigma_
         else:
             raise ValueError("expected an (H,W) or (H,W,C) array, got shape %r" % (img.shape,))
         x = np.ascontiguousarray(x, dtype=np.float32)
-        _check_image_size(*x.shape[-2:])
-        opts = _build_options(x.shape[1], n_iter, c, b, alpha, beta, sigma_r, sigma_s, ker_size, q, n_angles,
-                              n_interpolated_angles, remove_halo, edgetaping, prefiltering, discard_saturation,
-                              multichannel_kernel, method, support, prefilter)
-        eng = get_engine(0 if device is None else int(device))
-        eng.set_stream(0)                                   # host arrays: the device's default stream
-        if verbose:
-            eng.profile_begin()
-        try:
-            res = eng.polyblur(x, opts, want_info=return_info)
-        finally:                                            # (a failed call must not leave the thread's context profiling)
-            prof = eng.profile_end() if verbose else None
-        if verbose:
-            _print_stage_times(prof, time() - start)
-        out, info = res if return_info else (res, None)
+        dt, temporaries = np.float32, "fp32"                  # (`temporaries` is about float16 tensors: arrays never read it)
+    else:
+        if not is_tensor(img):
+            raise TypeError("img must be a numpy.ndarray or a torch.Tensor")
+        import torch
+        if img.dim() != 4:
+            raise ValueError("expected a (B,C,H,W) tensor, got shape %r" % (tuple(img.shape),))
+        if img.dtype not in (torch.float32, torch.float16):
+            raise TypeError("tensor dtype must be float32 or float16 (the reference is float32-only)")
+        if wants_grad(img):
+            return _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_interpolated_angles, remove_halo, edgetaping,
+                                     prefiltering, discard_saturation, multichannel_kernel, method, support, return_info, temporaries)
+        x, dt = img, (np.float32 if img.dtype == torch.float32 else np.float16)
+    check_image_size(*x.shape[-2:])
+    if temporaries == "fp16" and dt != np.float16:
+        raise ValueError("temporaries='fp16' applies to float16 images only")
+    opts = build_options(x.shape[1], n_iter, c, b, alpha, beta, sigma_r, sigma_s, ker_size, q, n_angles,
+                         n_interpolated_angles, remove_halo, edgetaping, prefiltering, discard_saturation,
+                         multichannel_kernel, method, support, prefilter, temporaries=temporaries)
+    out, info, prof = _run(x, dt, opts, return_info, device, verbose)
+    if verbose:
+        _print_stage_times(prof, time() - start)
+    if array:
         # utils.to_array (utils.py:24-31): squeeze, CHW -> HWC
         out = np.squeeze(out)
         if out.ndim == 3:
             out = np.ascontiguousarray(np.moveaxis(out, 0, -1))
-        return (out, _info_to_dicts(info, n_angles, n_interpolated_angles)) if return_info else out
-
-    if not _is_torch_tensor(img):
-        raise TypeError("img must be a numpy.ndarray or a torch.Tensor")
-    import torch
-    if img.dim() != 4:
-        raise ValueError("expected a (B,C,H,W) tensor, got shape %r" % (tuple(img.shape),))
-    if img.dtype not in (torch.float32, torch.float16):
-        raise TypeError("tensor dtype must be float32 or float16 (the reference is float32-only)")
-    if torch.is_grad_enabled() and img.requires_grad:
-        return _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_interpolated_angles, remove_halo, edgetaping,
-                                 prefiltering, discard_saturation, multichannel_kernel, method, support, return_info, temporaries)
-    _check_image_size(*img.shape[-2:])
-    if temporaries == "fp16" and img.dtype != torch.float16:
-        raise ValueError("temporaries='fp16' applies to float16 images only")
-    opts = _build_options(img.shape[1], n_iter, c, b, alpha, beta, sigma_r, sigma_s, ker_size, q, n_angles,
-                          n_interpolated_angles, remove_halo, edgetaping, prefiltering, discard_saturation,
-                          multichannel_kernel, method, support, prefilter, temporaries=temporaries)
-    dtype = capi.PB_F32 if img.dtype == torch.float32 else capi.PB_F16
-    if img.is_cuda:
-        dev = img.device.index if img.device.index is not None else torch.cuda.current_device()
-        eng = get_engine(dev)
-        xin = img.contiguous()
-        out = torch.empty_like(xin)
-        with torch.cuda.device(dev):
-            eng.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-            if verbose:
-                eng.profile_begin()
-            try:
-                info = eng.polyblur_ptr(xin.data_ptr(), out.data_ptr(), dtype, xin.shape, opts, want_info=return_info)
-            finally:                                        # (a failed call must not leave the thread's context profiling)
-                prof = eng.profile_end() if verbose else None
-    else:
-        eng = get_engine(0 if device is None else int(device))
-        eng.set_stream(0)
-        if verbose:
-            eng.profile_begin()
-        arr = img.detach().contiguous().numpy()
-        try:
-            res = eng.polyblur(arr, opts, want_info=return_info)
-        finally:
-            prof = eng.profile_end() if verbose else None
-        o, info = res if return_info else (res, None)
-        out = torch.from_numpy(o)
-    if verbose:
-        _print_stage_times(prof, time() - start)
     return (out, _info_to_dicts(info, n_angles, n_interpolated_angles)) if return_info else out
 
 
@@ -210,40 +133,36 @@ def _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_i
     (nonblind.py; 4.7) with the halo mask where asked (halo.py; 4.9), clip, n_iter times (deblurring.py:54-90).  Every refusal
     comes before any device work."""
     import torch
-    from .estimation import gaussian_blur_estimation
-    from .nonblind import _refuse_under_grad, inverse_filtering_rank3
     what = "polyblur_deblurring"
     if remove_halo and not (img.is_cuda and img.dtype == torch.float32):     # (the stage's device check first: its reason names the stage)
-        _refuse_under_grad(what + "(remove_halo=True)", "halo masking is differentiated for float32 ROCm tensors only")
-    for flag, name, why in ((edgetaping, "edgetaping", "the edgetaper is not differentiated"),
+        refuse_under_grad(what + "(remove_halo=True)", HALO_ONLY)
+    for flag, name, why in ((edgetaping, "edgetaping", NO_EDGETAPER),
                             (prefiltering, "prefiltering", "the edge-aware prefilters are not differentiated")):
         if flag:
-            _refuse_under_grad("%s(%s=True)" % (what, name), why)
+            refuse_under_grad("%s(%s=True)" % (what, name), why)
     if q > 0:
-        _refuse_under_grad("%s(q=%g)" % (what, q), "the backward of torch.quantile is not built -- pass q=0, which is what the blind driver defaults to")
+        refuse_under_grad("%s(q=%g)" % (what, q), NO_QUANTILE)
     if method == "direct_separable":
-        _refuse_under_grad(what + "(method='direct_separable')", "the x-t separable approximation is not differentiated")
+        refuse_under_grad(what + "(method='direct_separable')", "the x-t separable approximation is not differentiated")
     if method not in ("fft", "direct"):
         raise ValueError("%s not implemented" % method)
     if not (isinstance(ker_size, (int, np.integer)) and 3 <= ker_size <= capi.PB_KSIZE and ker_size % 2 == 1):
-        _refuse_under_grad("%s(ker_size=%r)" % (what, ker_size), "gradients are built for odd kernel sizes from 3 to 25")
+        refuse_under_grad("%s(ker_size=%r)" % (what, ker_size), "gradients are built for odd kernel sizes from 3 to 25")
     if support != "full":
-        _refuse_under_grad("%s(support=%r)" % (what, support), "gradients are built for support='full'")
+        refuse_under_grad("%s(support=%r)" % (what, support), "gradients are built for support='full'")
     if temporaries != "fp32":
-        _refuse_under_grad("%s(temporaries=%r)" % (what, temporaries), "gradients are built for float32 images and temporaries")
+        refuse_under_grad("%s(temporaries=%r)" % (what, temporaries), "gradients are built for float32 images and temporaries")
     if return_info:
-        _refuse_under_grad(what + "(return_info=True)", "the records are not part of the graph -- call gaussian_blur_estimation for the kernels")
+        refuse_under_grad(what + "(return_info=True)", "the records are not part of the graph -- call gaussian_blur_estimation for the kernels")
     if img.dtype == torch.float16:
-        _refuse_under_grad(what + " of a float16 image", "gradients are built for float32 images")
+        refuse_under_grad(what + " of a float16 image", FLOAT32_ONLY)
     if not img.is_cuda:
-        _refuse_under_grad(what, "img requires grad and is a CPU tensor -- gradients are built for ROCm tensors only")
+        refuse_under_grad(what, CPU_WITH_GRAD % "img")
     if not (isinstance(n_iter, (int, np.integer)) and n_iter >= 0):
         raise ValueError("n_iter must be an integer >= 0")
     x = img
-    grad_img = None
-    if remove_halo and n_iter > 0:                           # of the original input, for every iteration (deblurring.py:61,83)
-        from .halo import fourier_gradients
-        grad_img = fourier_gradients(img)
+    # (the halo mask's gradient planes are those of the original input, for every iteration: deblurring.py:61,83)
+    grad_img = fourier_gradients(img) if remove_halo and n_iter > 0 else None
     for _ in range(int(n_iter)):
         kernel = gaussian_blur_estimation(x, q=0, n_angles=n_angles, n_interpolated_angles=n_interpolated_angles, c=c, b=b,
                                           ker_size=ker_size, discard_saturation=discard_saturation, multichannel=multichannel_kernel)
@@ -262,7 +181,8 @@ def polyblur_deblurring_uint8(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, 
 
     ``numpy.ndarray`` uint8 (H,W) / (H,W,C) -> same shape uint8;  ``torch.Tensor`` uint8 (B,C,H,W) -> same."""
     start = time()
-    if isinstance(img, np.ndarray):
+    array = isinstance(img, np.ndarray)
+    if array:
         if img.dtype != np.uint8:
             raise TypeError("expected a uint8 image, got %s" % img.dtype)
         if img.ndim == 2:
@@ -271,37 +191,24 @@ def polyblur_deblurring_uint8(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, 
             x = img[None]
         else:
             raise ValueError("expected an (H,W) or (H,W,C) array, got shape %r" % (img.shape,))
-        opts = _build_options(x.shape[3], n_iter, c, b, alpha, beta, sigma_r, sigma_s, ker_size, q, n_angles,
-                              n_interpolated_angles, remove_halo, edgetaping, prefiltering, discard_saturation,
-                              multichannel_kernel, method, support, prefilter)
-        eng = get_engine(0 if device is None else int(device))
-        eng.set_stream(0)
-        res = eng.polyblur_u8_hwc(x, opts, want_info=return_info)
-        out, info = res if return_info else (res, None)
-        out = out.reshape(img.shape)
+        C = x.shape[3]
     else:
-        if not _is_torch_tensor(img):
+        if not is_tensor(img):
             raise TypeError("img must be a numpy.ndarray or a torch.Tensor")
         import torch
         if img.dim() != 4 or img.dtype != torch.uint8:
             raise TypeError("expected a (B,C,H,W) uint8 tensor")
-        opts = _build_options(img.shape[1], n_iter, c, b, alpha, beta, sigma_r, sigma_s, ker_size, q, n_angles,
-                              n_interpolated_angles, remove_halo, edgetaping, prefiltering, discard_saturation,
-                              multichannel_kernel, method, support, prefilter)
-        if img.is_cuda:
-            dev = img.device.index if img.device.index is not None else torch.cuda.current_device()
-            eng = get_engine(dev)
-            xin = img.contiguous()
-            out = torch.empty_like(xin)
-            with torch.cuda.device(dev):
-                eng.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-                info = eng.polyblur_ptr(xin.data_ptr(), out.data_ptr(), capi.PB_U8, xin.shape, opts, want_info=return_info)
-        else:
-            eng = get_engine(0 if device is None else int(device))
-            eng.set_stream(0)
-            res = eng.polyblur(img.detach().contiguous().numpy(), opts, want_info=return_info)
-            o, info = res if return_info else (res, None)
-            out = torch.from_numpy(o)
+        C = img.shape[1]
+    opts = build_options(C, n_iter, c, b, alpha, beta, sigma_r, sigma_s, ker_size, q, n_angles,
+                         n_interpolated_angles, remove_halo, edgetaping, prefiltering, discard_saturation,
+                         multichannel_kernel, method, support, prefilter)
+    if array:                                               # (interleaved bytes: planarised and re-interleaved on the device)
+        with bound_engine(None, device) as eng:
+            res = eng.polyblur_u8_hwc(x, opts, want_info=return_info)
+        out, info = res if return_info else (res, None)
+        out = out.reshape(img.shape)
+    else:
+        out, info, _ = _run(img, np.uint8, opts, return_info, device)
     if verbose:
         print('-- polyblur (hip, uint8): %1.5f s' % (time() - start))
     return (out, _info_to_dicts(info, n_angles, n_interpolated_angles)) if return_info else out
@@ -345,10 +252,8 @@ def _device_index(device):
 
 def _patchwise_deblurring(images, patch_size, overlap, batch_size, kwargs, device=None):
     """PolyblurDeblurring.forward, patch branch (deblurring.py:269-340, fix-forward)."""
-    import ctypes as C
-
     import torch
-    if not _is_torch_tensor(images) or images.dim() != 4:
+    if not is_tensor(images) or images.dim() != 4:
         raise ValueError("patch decomposition expects a (B,C,H,W) tensor")
     if images.dtype not in (torch.float32, torch.float16):
         raise TypeError("tensor dtype must be float32 or float16")
@@ -384,27 +289,21 @@ def _patchwise_deblurring(images, patch_size, overlap, batch_size, kwargs, devic
     g = patch_grid(h, w, patch_size, overlap)
     if g["ph"] < 2 or g["pw"] < 2 or g["step_h"] < 1 or g["step_w"] < 1:
         raise ValueError("patch size / overlap incompatible: patches of at least 2x2 with a positive step are needed")
-    eng = get_engine(dev)
     dtype = capi.PB_F32 if x.dtype == torch.float32 else capi.PB_F16
     n_p = g["n_i"] * g["n_j"]
     wy = torch.from_numpy(kaiser_window_periodic(g["ph"])).to(x.device)
     wx = torch.from_numpy(kaiser_window_periodic(g["pw"])).to(x.device)
     restored = torch.empty((n_p * B, Cc, g["ph"], g["pw"]), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(dev):
-        eng.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    with bound_engine(x) as eng:
         group = max(1, int(batch_size))
         for first in range(0, n_p, group):                       # :310 groups of `batch_size` patches
             count = min(group, n_p - first)
             patches = torch.empty((count * B, Cc, g["ph"], g["pw"]), dtype=x.dtype, device=x.device)
-            eng._check(eng.lib.pb_extract_patches(eng.ctx, x.data_ptr(), patches.data_ptr(), dtype, B, Cc, h, w, g["ph"],
-                                                  g["pw"], g["step_h"], g["step_w"], g["n_i"], g["n_j"], g["pad_top"],
-                                                  g["pad_left"], first, count))
+            eng.extract_patches_ptr(x.data_ptr(), patches.data_ptr(), dtype, x.shape, g, first, count)
             restored[first * B:(first + count) * B] = polyblur_deblurring(patches, **kwargs)
         out = torch.empty_like(x)
-        eng._check(eng.lib.pb_overlap_add(eng.ctx, restored.data_ptr(), out.data_ptr(), dtype, B, Cc, h, w, g["ph"], g["pw"],
-                                          g["step_h"], g["step_w"], g["n_i"], g["n_j"], g["pad_top"], g["pad_left"],
-                                          C.c_void_p(wy.data_ptr()), C.c_void_p(wx.data_ptr())))
-        torch.cuda.current_stream(dev).synchronize()             # wy / wx / restored must outlive the kernels
+        eng.overlap_add_ptr(restored.data_ptr(), out.data_ptr(), dtype, x.shape, g, wy.data_ptr(), wx.data_ptr())
+        eng.synchronize()                                        # wy / wx / restored must outlive the kernels
     return out if was_cuda else out.cpu()
 
 
@@ -441,12 +340,9 @@ class PolyblurDeblurring(_Base):
                 q=0.0, n_angles=6, n_interpolated_angles=30, remove_halo=False, edgetaping=False, prefiltering=False,
                 discard_saturation=False, multichannel_kernel=False, method='fft', device=None, **extras):
         if self.patch_decomposition:
-            if _is_torch_tensor(images) and images.requires_grad:
-                import torch
-                if torch.is_grad_enabled():
-                    from .nonblind import _refuse_under_grad
-                    _refuse_under_grad("PolyblurDeblurring(patch_decomposition=True)", "the patch extraction and the windowed overlap-add "
-                                       "(pb_extract_patches, pb_overlap_add) are not differentiated")
+            if wants_grad(images):
+                refuse_under_grad("PolyblurDeblurring(patch_decomposition=True)", "the patch extraction and the windowed overlap-add "
+                                  "(pb_extract_patches, pb_overlap_add) are not differentiated")
             return _patchwise_deblurring(images, self.patch_size, self.patch_overlap, self.batch_size,
                                          dict(n_iter=n_iter, c=c, b=b, alpha=alpha, beta=beta, ker_size=ker_size,
                                               sigma_s=sigma_s, sigma_r=sigma_r, remove_halo=remove_halo,

@@ -177,14 +177,34 @@ class Engine:
         return info
 
     # ---- numpy conveniences (host arrays in, host arrays out) -------------------------------
+    def host_call(self, x: np.ndarray, call, extra=(), outputs=None, sync=True):
+        """The one upload / call / download of host data: x goes to "np.in", each (pool name, array) of `extra` to its buffer as
+        float32; call(in_ptr, out_ptrs, extra_ptrs) runs on the context's stream; `outputs` -- (pool name, shape, dtype) each,
+        by default one like x in "np.out" -- come back as arrays.  -> (outputs, what call returned).  `sync`: wait for the
+        stream before the download (which waits for it as well: whether a method says so is kept as it was written)."""
+        din = self.to_device("np.in", x)
+        spec = [("np.out", x.shape, x.dtype)] if outputs is None else outputs
+        bufs = [self.buffer(name, int(np.prod(shape)) * np.dtype(dt).itemsize) for name, shape, dt in spec]
+        ex = [self.to_device(name, np.ascontiguousarray(a, np.float32)).ptr for name, a in extra]
+        ret = call(din.ptr, [b.ptr for b in bufs], ex)
+        if sync:
+            self.synchronize()
+        return [b.download(shape, dt) for b, (_, shape, dt) in zip(bufs, spec)], ret
+
+    def _one(self, x, call, extra=()):
+        """host_call with one output like x, which is all that most conveniences need"""
+        return self.host_call(x, lambda i, o, ex: call(i, o[0], *ex), extra)[0][0]
+
+    @staticmethod
+    def _grad0(grad0):
+        """the halo mask's gradient planes of the original image as `extra` of host_call"""
+        return (("np.g0x", grad0[0]), ("np.g0y", grad0[1]))
+
     def polyblur(self, x: np.ndarray, opts: capi.pb_options, want_info=False):
         x = np.ascontiguousarray(x)
         if x.dtype not in _DT:
             x = x.astype(np.float32)
-        din = self.to_device("np.in", x)
-        dout = self.buffer("np.out", x.nbytes)
-        info = self.polyblur_ptr(din.ptr, dout.ptr, _DT[x.dtype], x.shape, opts, want_info)
-        out = dout.download(x.shape, x.dtype)
+        (out,), info = self.host_call(x, lambda i, o, ex: self.polyblur_ptr(i, o[0], _DT[x.dtype], x.shape, opts, want_info), sync=False)
         return (out, info) if want_info else out
 
     def polyblur_u8_hwc(self, imgs: np.ndarray, opts: capi.pb_options, want_info=False):
@@ -228,56 +248,32 @@ class Engine:
 
     def estimate_blur(self, x: np.ndarray, opts: capi.pb_options) -> np.ndarray:
         x = np.ascontiguousarray(x)
-        B, Cc, H, W = x.shape
-        din = self.to_device("np.in", x)
-        buf = self.info_buffer("np.info", B)
-        self._check(self.lib.pb_estimate_blur(self.ctx, din.ptr, _DT[x.dtype], B, Cc, H, W, C.byref(opts), buf.ptr))
-        return self.read_info(buf, B)
+        return self.host_call(x, lambda i, o, ex: self.estimate_blur_ptr(i, _DT[x.dtype], x.shape, opts, o[0]),
+                              outputs=[("np.info", (x.shape[0],), capi.INFO_DTYPE)])[0][0]
 
     def fourier_gradients(self, x: np.ndarray):
         x = np.ascontiguousarray(x, np.float32)
-        H, W = x.shape[-2:]
-        P = int(np.prod(x.shape[:-2])) if x.ndim > 2 else 1
-        din = self.to_device("np.in", x)
-        gx = self.buffer("np.gx", x.nbytes)
-        gy = self.buffer("np.gy", x.nbytes)
-        self._check(self.lib.pb_fourier_gradients(self.ctx, din.ptr, P, H, W, gx.ptr, gy.ptr))
-        self.synchronize()
-        return gx.download(x.shape, np.float32), gy.download(x.shape, np.float32)
+        return tuple(self.host_call(x, lambda i, o, ex: self.fourier_gradients_ptr(i, x.shape, o[0], o[1]),
+                                    outputs=[("np.gx", x.shape, np.float32), ("np.gy", x.shape, np.float32)])[0])
 
     def inverse_filter(self, x: np.ndarray, info: DeviceBuffer, alpha, beta, boundary=capi.PB_WRAP, edgetaping=False,
                        remove_halo=False, grad0=None) -> np.ndarray:
         x = np.ascontiguousarray(x)
         B, Cc, H, W = x.shape
-        din = self.to_device("np.in", x)
-        dout = self.buffer("np.out", x.nbytes)
-        g0x = g0y = None
-        if remove_halo:
-            g0x = self.to_device("np.g0x", np.ascontiguousarray(grad0[0], np.float32)).ptr
-            g0y = self.to_device("np.g0y", np.ascontiguousarray(grad0[1], np.float32)).ptr
-        self._check(self.lib.pb_inverse_filter(self.ctx, din.ptr, dout.ptr, _DT[x.dtype], B, Cc, H, W, info.ptr,
-                                               float(alpha), float(beta), int(boundary), int(bool(edgetaping)),
-                                               int(bool(remove_halo)), g0x, g0y))
-        self.synchronize()
-        return dout.download(x.shape, x.dtype)
+        extra = self._grad0(grad0) if remove_halo else ()     # (here the planes are the caller's to give: none is an error)
+        return self._one(x, lambda i, o, g0x=None, g0y=None: self._check(self.lib.pb_inverse_filter(
+            self.ctx, i, o, _DT[x.dtype], B, Cc, H, W, info.ptr, float(alpha), float(beta), int(boundary), int(bool(edgetaping)),
+            int(bool(remove_halo)), g0x, g0y)), extra)
 
     def convolve2d(self, xp: np.ndarray, info: DeviceBuffer, boundary=capi.PB_WRAP) -> np.ndarray:
         xp = np.ascontiguousarray(xp, np.float32)
         B, Cc, Hp, Wp = xp.shape
-        din = self.to_device("np.in", xp)
-        dout = self.buffer("np.out", xp.nbytes)
-        self._check(self.lib.pb_convolve2d(self.ctx, din.ptr, dout.ptr, B, Cc, Hp, Wp, info.ptr, int(boundary)))
-        self.synchronize()
-        return dout.download(xp.shape, np.float32)
+        return self._one(xp, lambda i, o: self._check(self.lib.pb_convolve2d(self.ctx, i, o, B, Cc, Hp, Wp, info.ptr, int(boundary))))
 
     def edgetaper(self, xp: np.ndarray, info: DeviceBuffer, boundary=capi.PB_WRAP) -> np.ndarray:
         xp = np.ascontiguousarray(xp, np.float32)
         B, Cc, Hp, Wp = xp.shape
-        din = self.to_device("np.in", xp)
-        dout = self.buffer("np.out", xp.nbytes)
-        self._check(self.lib.pb_edgetaper(self.ctx, din.ptr, dout.ptr, B, Cc, Hp, Wp, info.ptr, int(boundary)))
-        self.synchronize()
-        return dout.download(xp.shape, np.float32)
+        return self._one(xp, lambda i, o: self._check(self.lib.pb_edgetaper(self.ctx, i, o, B, Cc, Hp, Wp, info.ptr, int(boundary))))
 
     # ---- caller-owned kernel sets (pb_taps): any kh x kw up to 49 x 49 ---------------------
     def set_taps(self, taps, support=capi.PB_SUPPORT_FULL) -> KernelSet:
@@ -348,57 +344,34 @@ class Engine:
         self._check(self.lib.pb_estimate_blur_backward(self.ctx, in_ptr, B, Cc, H, W, C.byref(opts), info_ptr, grad_kernel_ptr,
                                                        grad_sigma_rho_ptr, int(ker_size), grad_in_ptr))
 
-    def _taps_call(self, x: np.ndarray, call):
-        x = np.ascontiguousarray(x)
-        din = self.to_device("np.in", x)
-        dout = self.buffer("np.out", x.nbytes)
-        call(din.ptr, dout.ptr)
-        self.synchronize()
-        return dout.download(x.shape, x.dtype)
-
     def convolve2d_taps(self, x: np.ndarray, ks: KernelSet, boundary=capi.PB_ZERO) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)
-        return self._taps_call(x, lambda i, o: self.convolve2d_taps_ptr(i, o, x.shape, ks, boundary))
+        return self._one(x, lambda i, o: self.convolve2d_taps_ptr(i, o, x.shape, ks, boundary))
 
     def edgetaper_taps(self, x: np.ndarray, ks: KernelSet, boundary=capi.PB_WRAP, n_tapers=3) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)
-        return self._taps_call(x, lambda i, o: self.edgetaper_taps_ptr(i, o, x.shape, ks, boundary, n_tapers))
+        return self._one(x, lambda i, o: self.edgetaper_taps_ptr(i, o, x.shape, ks, boundary, n_tapers))
 
     def inverse_filter_taps(self, x: np.ndarray, ks: KernelSet, alpha, beta, boundary=capi.PB_ZERO, edgetaping=False,
                             remove_halo=False, grad0=None) -> np.ndarray:
         x = np.ascontiguousarray(x)
-        g0x = g0y = None
-        if remove_halo and grad0 is not None:
-            g0x = self.to_device("np.g0x", np.ascontiguousarray(grad0[0], np.float32)).ptr
-            g0y = self.to_device("np.g0y", np.ascontiguousarray(grad0[1], np.float32)).ptr
-        return self._taps_call(x, lambda i, o: self.inverse_filter_taps_ptr(i, o, _DT[x.dtype], x.shape, ks, alpha, beta, boundary,
-                                                                            edgetaping, remove_halo, g0x, g0y))
+        return self._one(x, lambda i, o, g0x=None, g0y=None: self.inverse_filter_taps_ptr(
+            i, o, _DT[x.dtype], x.shape, ks, alpha, beta, boundary, edgetaping, remove_halo, g0x, g0y), self._grad0(grad0) if remove_halo and grad0 is not None else ())
 
     def compute_polynomial_taps(self, x: np.ndarray, ks: KernelSet, alpha, beta, boundary=capi.PB_WRAP, not_symmetric=False) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)
-        return self._taps_call(x, lambda i, o: self.compute_polynomial_taps_ptr(i, o, x.shape, ks, alpha, beta, boundary, not_symmetric))
+        return self._one(x, lambda i, o: self.compute_polynomial_taps_ptr(i, o, x.shape, ks, alpha, beta, boundary, not_symmetric))
 
     def inverse_filter_phase_taps(self, x: np.ndarray, ks: KernelSet, alpha, beta, edgetaping=False, remove_halo=False,
                                   grad0=None) -> np.ndarray:
         x = np.ascontiguousarray(x)
-        g0x = g0y = None
-        if remove_halo and grad0 is not None:
-            g0x = self.to_device("np.g0x", np.ascontiguousarray(grad0[0], np.float32)).ptr
-            g0y = self.to_device("np.g0y", np.ascontiguousarray(grad0[1], np.float32)).ptr
-        return self._taps_call(x, lambda i, o: self.inverse_filter_phase_taps_ptr(i, o, _DT[x.dtype], x.shape, ks, alpha, beta,
-                                                                              edgetaping, remove_halo, g0x, g0y))
+        return self._one(x, lambda i, o, g0x=None, g0y=None: self.inverse_filter_phase_taps_ptr(
+            i, o, _DT[x.dtype], x.shape, ks, alpha, beta, edgetaping, remove_halo, g0x, g0y), self._grad0(grad0) if remove_halo and grad0 is not None else ())
 
     def halo_mask(self, x, y, g0x, g0y) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)
-        B, Cc, H, W = x.shape
-        dx = self.to_device("np.in", x)
-        dy = self.to_device("np.y", np.ascontiguousarray(y, np.float32))
-        dgx = self.to_device("np.g0x", np.ascontiguousarray(g0x, np.float32))
-        dgy = self.to_device("np.g0y", np.ascontiguousarray(g0y, np.float32))
-        dout = self.buffer("np.out", x.nbytes)
-        self._check(self.lib.pb_halo_mask(self.ctx, dx.ptr, dy.ptr, dgx.ptr, dgy.ptr, dout.ptr, B, Cc, H, W))
-        self.synchronize()
-        return dout.download(x.shape, np.float32)
+        return self._one(x, lambda i, o, y_ptr, gx_ptr, gy_ptr: self.halo_mask_ptr(i, y_ptr, gx_ptr, gy_ptr, o, x.shape),
+                         (("np.y", y),) + self._grad0((g0x, g0y)))
 
     # ---- halo masking and the spectral derivative on device pointers, and their backward passes ----------
     def fourier_gradients_ptr(self, in_ptr: int, shape, gx_ptr, gy_ptr):
@@ -426,32 +399,36 @@ class Engine:
     def dt_recursive_filter(self, x: np.ndarray, sigma_s=60.0, sigma_r=0.4, num_iterations=3, joint=None) -> np.ndarray:
         x = np.ascontiguousarray(x)
         B, Cc, H, W = x.shape
-        din = self.to_device("np.in", x)
         dj = self.to_device("np.joint", np.ascontiguousarray(joint, x.dtype)).ptr if joint is not None else None
-        dout = self.buffer("np.out", x.nbytes)
-        self._check(self.lib.pb_dt_recursive_filter(self.ctx, din.ptr, dj, dout.ptr, _DT[x.dtype], B, Cc, H, W,
-                                                    float(sigma_s), float(sigma_r), int(num_iterations)))
-        self.synchronize()
-        return dout.download(x.shape, x.dtype)
+        return self._one(x, lambda i, o: self._check(self.lib.pb_dt_recursive_filter(
+            self.ctx, i, dj, o, _DT[x.dtype], B, Cc, H, W, float(sigma_s), float(sigma_r), int(num_iterations))))
 
     def dt_normalized_convolution(self, x: np.ndarray, sigma_s=60.0, sigma_r=0.4, num_iterations=3) -> np.ndarray:
         x = np.ascontiguousarray(x)
         B, Cc, H, W = x.shape
-        din = self.to_device("np.in", x)
-        dout = self.buffer("np.out", x.nbytes)
-        self._check(self.lib.pb_dt_normalized_convolution(self.ctx, din.ptr, dout.ptr, _DT[x.dtype], B, Cc, H, W,
-                                                          float(sigma_s), float(sigma_r), int(num_iterations)))
-        self.synchronize()
-        return dout.download(x.shape, x.dtype)
+        return self._one(x, lambda i, o: self._check(self.lib.pb_dt_normalized_convolution(
+            self.ctx, i, o, _DT[x.dtype], B, Cc, H, W, float(sigma_s), float(sigma_r), int(num_iterations))))
 
     def bilateral5(self, x: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x)
         B, Cc, H, W = x.shape
-        din = self.to_device("np.in", x)
-        dout = self.buffer("np.out", x.nbytes)
-        self._check(self.lib.pb_bilateral5(self.ctx, din.ptr, dout.ptr, _DT[x.dtype], B, Cc, H, W))
-        self.synchronize()
-        return dout.download(x.shape, x.dtype)
+        return self._one(x, lambda i, o: self._check(self.lib.pb_bilateral5(self.ctx, i, o, _DT[x.dtype], B, Cc, H, W)))
+
+    # ---- the patch lattice of PolyblurDeblurring(patch_decomposition=True) on device pointers -----------------------------
+    def extract_patches_ptr(self, in_ptr: int, patches_ptr: int, dtype: int, shape, grid: dict, first: int, count: int):
+        """patches first .. first + count - 1 of every image, replicate-padded to the lattice `grid` (deblurring.patch_grid;
+        pb_extract_patches); asynchronous"""
+        B, Cc, H, W = (int(v) for v in shape)
+        g = grid
+        self._check(self.lib.pb_extract_patches(self.ctx, in_ptr, patches_ptr, dtype, B, Cc, H, W, g["ph"], g["pw"], g["step_h"], g["step_w"],
+                                                g["n_i"], g["n_j"], g["pad_top"], g["pad_left"], int(first), int(count)))
+
+    def overlap_add_ptr(self, patches_ptr: int, out_ptr: int, dtype: int, shape, grid: dict, wy_ptr: int, wx_ptr: int):
+        """the windowed, normalised overlap-add of all patches, clamped and cropped (pb_overlap_add); asynchronous"""
+        B, Cc, H, W = (int(v) for v in shape)
+        g = grid
+        self._check(self.lib.pb_overlap_add(self.ctx, patches_ptr, out_ptr, dtype, B, Cc, H, W, g["ph"], g["pw"], g["step_h"], g["step_w"],
+                                            g["n_i"], g["n_j"], g["pad_top"], g["pad_left"], C.c_void_p(wy_ptr), C.c_void_p(wx_ptr)))
 
     def profile_begin(self):
         self._check(self.lib.pb_profile_begin(self.ctx))

@@ -25,6 +25,7 @@ import torch
 
 import autograd_ref as ar
 import estimation_grad_ref as er
+from frontend_cases import no_device
 
 
 def golden_cases(golden, kind=None):
@@ -155,17 +156,10 @@ def test_symbol_is_declared_and_bound():
 
 
 @pytest.fixture
-def no_library(monkeypatch):
+def no_library():
     """any attempt to load the library or to make an engine is an error"""
-    from polyblur_amd import _capi as capi
-    import polyblur_amd.engine as engine
-
-    def boom(*a, **k):
-        raise AssertionError("device work before the refusal")
-    monkeypatch.setattr(capi, "load_library", boom)
-    for mod in ("polyblur_amd.engine", "polyblur_amd.estimation", "polyblur_amd.nonblind", "polyblur_amd.deblurring"):
-        monkeypatch.setattr(mod + ".get_engine", boom)
-    return engine
+    with no_device(AssertionError("device work before the refusal")):
+        yield
 
 
 def test_refusals_of_gaussian_blur_estimation(no_library):

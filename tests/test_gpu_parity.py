@@ -2,6 +2,7 @@
 against the CPU oracle on the same seeded inputs.  Tolerances are fp32 (stated per check);
 the north star asks for end-to-end agreement with the reference's NumPy path within a stated
 fp32 tolerance: 2e-5 max-abs after n_iter=3 with the identical theta sequence."""
+import functools
 import os
 
 import numpy as np
@@ -711,21 +712,102 @@ def test_constant_image_is_guarded():
     assert np.isfinite(out).all() and maxabs(out, x) < 1e-6
 
 
-def test_non_contiguous_and_stream(eng):
+def _strided(t):
+    """the same values as a strided view of transposed storage"""
+    v = t.transpose(-1, -2).contiguous().transpose(-1, -2)
+    assert not v.is_contiguous() and v.shape == t.shape
+    return v
+
+
+@functools.lru_cache(maxsize=None)
+def _front_end_cases():
+    """name -> (operands as arrays, call(polyblur_amd, operands as tensors), the operands to differentiate): every public function,
+    the differentiable ones with their gradients.  (2,3,24,40) images and a (1,1,5,7) kernel -- small, odd against every tile, more than
+    one plane and image -- but for the first case, which is the one this test began with."""
+    rng = np.random.default_rng(29)
+    big, _ = synthetic_blurry_batch(2, 3, 64, 96, seed0=3)
+    img, _ = synthetic_blurry_batch(2, 3, 24, 40, seed0=5)
+    other = np.clip(img + rng.normal(0, 0.05, img.shape), 0, 1).astype(np.float32)
+    gx, gy = (rng.normal(0, 0.1, img.shape).astype(np.float32) for _ in range(2))
+    k = rng.random((1, 1, 5, 7)).astype(np.float32)
+    k /= k.sum()
+    ik = dict(img=img, kernel=k)
+    halo = dict(img=img, kernel=k, gx=gx, gy=gy)
+    blind = dict(n_iter=1, **KW)
+    return {
+        "polyblur_deblurring": (dict(img=big), lambda pa, o: pa.polyblur_deblurring(o["img"], **blind), None),
+        "polyblur_deblurring-small": (dict(img=img), lambda pa, o: pa.polyblur_deblurring(o["img"], **blind), None),
+        "polyblur_deblurring-float16": (dict(img=img.astype(np.float16)), lambda pa, o: pa.polyblur_deblurring(o["img"], **blind), None),
+        "polyblur_deblurring_uint8": (dict(img=(img * 255).astype(np.uint8)), lambda pa, o: pa.polyblur_deblurring_uint8(o["img"], **blind), None),
+        "PolyblurDeblurring": (dict(img=img), lambda pa, o: pa.PolyblurDeblurring()(o["img"], **blind), None),
+        "PolyblurDeblurring-patches": (dict(img=img), lambda pa, o: pa.PolyblurDeblurring(True, 16, 0.25, 2)(o["img"], **blind), None),
+        "polyblur_deblurring-n_iter=2-remove_halo": (dict(img=img), lambda pa, o: pa.polyblur_deblurring(o["img"], n_iter=2, remove_halo=True, **KW), ("img",)),
+        "convolve2d": (ik, lambda pa, o: pa.convolve2d(o["img"], o["kernel"], method="direct"), ("img", "kernel")),
+        "edgetaper": (ik, lambda pa, o: pa.edgetaper(o["img"], o["kernel"]), None),
+        "compute_polynomial": (ik, lambda pa, o: pa.compute_polynomial(o["img"], o["kernel"], 6, 1), ("img", "kernel")),
+        "compute_polynomial-not_symmetric": (ik, lambda pa, o: pa.compute_polynomial(o["img"], o["kernel"], 6, 1, not_symmetric=True), None),
+        "inverse_filtering_rank3": (ik, lambda pa, o: pa.inverse_filtering_rank3(o["img"], o["kernel"], 6, 1, method="fft"), ("img", "kernel")),
+        "inverse_filtering_rank3-remove_halo": (halo, lambda pa, o: pa.inverse_filtering_rank3(o["img"], o["kernel"], 6, 1, remove_halo=True,
+                                                                                             grad_img=(o["gx"], o["gy"])), ("img", "kernel", "gx", "gy")),
+        "inverse_filtering_rank3-do_edgetaper": (ik, lambda pa, o: pa.inverse_filtering_rank3(o["img"], o["kernel"], 6, 1, do_edgetaper=True, method="fft"), None),
+        "inverse_filtering_nonsymmetric": (halo, lambda pa, o: pa.inverse_filtering_nonsymmetric(o["img"], o["kernel"], 6, 1, remove_halo=True,
+                                                                                               grad_img=(o["gx"], o["gy"])), None),
+        "gaussian_blur_estimation": (dict(img=img), lambda pa, o: pa.gaussian_blur_estimation(o["img"], q=0), ("img",)),
+        "gaussian_blur_estimation-parameters": (dict(img=img), lambda pa, o: pa.gaussian_blur_estimation(o["img"], q=0, return_2d_filters=False), ("img",)),
+        "fourier_gradients": (dict(img=img), lambda pa, o: pa.fourier_gradients(o["img"]), ("img",)),
+        "halo_masking": (dict(img=img, imout=other, gx=gx, gy=gy), lambda pa, o: pa.halo_masking(o["img"], o["imout"], (o["gx"], o["gy"])),
+                         ("img", "imout", "gx", "gy")),
+        "halo_masking-own-gradients": (dict(img=img, imout=other), lambda pa, o: pa.halo_masking(o["img"], o["imout"]), ("img", "imout")),
+    }
+
+
+_FRONT_END = ["polyblur_deblurring", "polyblur_deblurring-small", "polyblur_deblurring-float16", "polyblur_deblurring_uint8", "PolyblurDeblurring",
+              "PolyblurDeblurring-patches", "polyblur_deblurring-n_iter=2-remove_halo", "convolve2d", "edgetaper", "compute_polynomial",
+              "compute_polynomial-not_symmetric", "inverse_filtering_rank3", "inverse_filtering_rank3-remove_halo",
+              "inverse_filtering_rank3-do_edgetaper", "inverse_filtering_nonsymmetric", "gaussian_blur_estimation",
+              "gaussian_blur_estimation-parameters", "fourier_gradients", "halo_masking", "halo_masking-own-gradients"]
+
+
+def test_the_front_end_table_is_whole():
+    assert sorted(_front_end_cases()) == sorted(_FRONT_END)
+
+
+@pytest.mark.parametrize("name", _FRONT_END)
+def test_non_contiguous_and_stream(eng, name):
+    """every public function gives the same bits -- outputs and, where it is differentiable, every input gradient under a fixed
+    upstream weight -- for contiguous ROCm tensors on the default stream, for strided views of transposed storage (image, kernel,
+    imout and grad_img alike) and for contiguous tensors under torch.cuda.stream(side)"""
     import torch
-    from polyblur_amd import polyblur_deblurring
-    x, _ = synthetic_blurry_batch(2, 3, 64, 96, seed0=3)
-    xt = torch.from_numpy(x).cuda()
-    a = polyblur_deblurring(xt, n_iter=1, **KW)
-    xs = torch.from_numpy(np.ascontiguousarray(x.transpose(0, 1, 3, 2))).cuda().permute(0, 1, 3, 2)   # strided view
-    assert not xs.is_contiguous()
-    b = polyblur_deblurring(xs, n_iter=1, **KW)
-    assert torch.equal(a, b)
-    st = torch.cuda.Stream()
-    with torch.cuda.stream(st):
-        c = polyblur_deblurring(xt, n_iter=1, **KW)
-    st.synchronize()
-    assert torch.equal(a, c)
+    import polyblur_amd as pa
+    arrays, call, leaves = _front_end_cases()[name]
+    side = torch.cuda.Stream()
+
+    def run(variant, grad):
+        ops = {n: torch.from_numpy(a).cuda() for n, a in arrays.items()}
+        if variant == "strided":
+            ops = {n: _strided(t) for n, t in ops.items()}
+        for n in (leaves if grad else ()):
+            ops[n].requires_grad_(True)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(side if variant == "stream" else torch.cuda.current_stream()), torch.set_grad_enabled(grad):
+            out = call(pa, ops)
+            outs = list(out) if isinstance(out, (tuple, list)) else [out]
+            if grad:
+                live = [o for o in outs if o.requires_grad]
+                assert live and all(o.grad_fn is not None for o in live)
+                rng = np.random.default_rng(31)                                  # (the same upstream weights for every variant)
+                sum((o * torch.from_numpy(rng.uniform(-1, 1, tuple(o.shape)).astype(np.float32)).cuda()).sum() for o in live).backward()
+        torch.cuda.synchronize()
+        return [o.detach() for o in outs] + ([ops[n].grad for n in leaves] if grad else [])
+
+    for grad in ((False, True) if leaves else (False,)):
+        base = run("contiguous", grad)
+        assert all(t is not None and bool(torch.isfinite(t.float()).all()) for t in base)
+        for variant in ("strided", "stream"):
+            got = run(variant, grad)
+            assert len(got) == len(base)
+            for i, (a, b) in enumerate(zip(base, got)):
+                assert torch.equal(a, b), (name, variant, "grad" if grad else "no grad", i)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import autograd_ref as ar
+from frontend_cases import no_device
 import halo_grad_ref as hg
 import halo_ref as hr
 
@@ -238,15 +239,10 @@ def test_symbols_names_and_header():
 
 
 @pytest.fixture
-def no_library(monkeypatch):
+def no_library():
     """any device work raises: a refusal must come first"""
-    from polyblur_amd import _capi as capi
-
-    def boom(*a, **k):
-        raise AssertionError("device work before the refusal")
-    monkeypatch.setattr(capi, "load_library", boom)
-    for mod in ("polyblur_amd.engine", "polyblur_amd.estimation", "polyblur_amd.nonblind", "polyblur_amd.deblurring", "polyblur_amd.halo"):
-        monkeypatch.setattr(mod + ".get_engine", boom)
+    with no_device(AssertionError("device work before the refusal")):
+        yield
 
 
 def test_refusals_that_remain(no_library):
