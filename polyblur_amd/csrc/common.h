@@ -363,6 +363,7 @@ int pb_tap_gradient_groups(int B, int C, int H, int W);
 // ------------------------------------------------------------------------------------
 // estimation (estimate.hip)
 // ------------------------------------------------------------------------------------
+constexpr int kMaxLineLength = 65536;          // longest line of the spectral derivative (pb_fft_length_supported, estimate.hip)
 int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H, int W,
                      const pb_options *opt, pb_blur_info *dev_info);
 int pb_make_sep_records(pb_ctx *ctx, int B, const pb_blur_info *dev_info, pb_blur_info *sep, int support, int ksize);
@@ -394,6 +395,36 @@ __device__ __forceinline__ unsigned pb_to_ubyte(float v) { return (unsigned)__fl
 template <> __device__ __forceinline__ void pb_st<unsigned char>(unsigned char *p, float v) { *p = (unsigned char)pb_to_ubyte(v); }
 template <> __device__ __forceinline__ void pb_st<float>(float *p, float v) { *p = v; }
 template <> __device__ __forceinline__ void pb_st<__half>(__half *p, float v) { *p = __float2half_rn(v); }
+
+// four consecutive samples as floats: one access of 16 bytes (fp32), 8 (fp16) or 4 (8-bit), on a boundary of that size
+template <typename T> __device__ __forceinline__ float4 pb_ld4(const T *p);
+template <> __device__ __forceinline__ float4 pb_ld4<float>(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+template <> __device__ __forceinline__ float4 pb_ld4<__half>(const __half *p) {
+    const uint2 u = *reinterpret_cast<const uint2 *>(p);
+    const __half2 a = *reinterpret_cast<const __half2 *>(&u.x), b = *reinterpret_cast<const __half2 *>(&u.y);
+    const float2 fa = __half22float2(a), fb = __half22float2(b);
+    return make_float4(fa.x, fa.y, fb.x, fb.y);
+}
+template <> __device__ __forceinline__ float4 pb_ld4<unsigned char>(const unsigned char *p) {
+    const unsigned u = *reinterpret_cast<const unsigned *>(p);
+    return make_float4(pb_from_ubyte(u & 255u), pb_from_ubyte((u >> 8) & 255u), pb_from_ubyte((u >> 16) & 255u), pb_from_ubyte(u >> 24));
+}
+template <typename T> __device__ __forceinline__ void pb_st4(T *p, float4 v);
+template <> __device__ __forceinline__ void pb_st4<unsigned char>(unsigned char *p, float4 v) {
+    *reinterpret_cast<unsigned *>(p) = pb_to_ubyte(v.x) | (pb_to_ubyte(v.y) << 8) | (pb_to_ubyte(v.z) << 16) | (pb_to_ubyte(v.w) << 24);
+}
+template <> __device__ __forceinline__ void pb_st4<float>(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
+template <> __device__ __forceinline__ void pb_st4<__half>(__half *p, float4 v) {
+    const __half2 a = __floats2half2_rn(v.x, v.y), b = __floats2half2_rn(v.z, v.w);
+    uint2 u;
+    u.x = *reinterpret_cast<const unsigned *>(&a);
+    u.y = *reinterpret_cast<const unsigned *>(&b);
+    *reinterpret_cast<uint2 *>(p) = u;
+}
+
+// One wave per output folds that output's `per_out` partial sums (pb_block_sum_to_first's, stage_math.h) in a fixed order:
+// out[blockIdx.x] = sum of partial[blockIdx.x * per_out ..], bit-reproducible.  Launched on 64 threads; defined in filters.hip
+__global__ __launch_bounds__(64) void pb_fold_partials_kernel(const float *__restrict__ partial, float *__restrict__ out, int per_out);
 
 // order-preserving float <-> uint encoding for atomicMin/atomicMax on floats
 __device__ __forceinline__ unsigned pb_f2ord(float f) {

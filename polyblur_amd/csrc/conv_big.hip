@@ -20,6 +20,7 @@
 // 2 Rx + 1 taps, Ry = kh / 2, Rx = kw / 2: a 3 x 49 kernel stages a 34-row tile and reads 3 tap rows.  The estimation's own
 // kernels are the case Ry == Rx.
 #include "conv_common.h"
+#include "stage_math.h"
 
 namespace {
 
@@ -29,17 +30,6 @@ constexpr int BK_ROWS = 2 * BK_R + 1;
 constexpr int BK_AC = 64;                // floats per stored autocorrelation (49 lags)
 constexpr int BG_TW = 64, BG_TH = 32, BG_NT = 256;
 static_assert(BK_ROWS == PB_KSIZE_MAX && BK_ROWS * BK_P == PB_BIG_TABLE && 2 * BK_AC == PB_BIG_ACORR, "common.h: BigTaps");
-
-__device__ float big_block_sum(float v, float *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int w = 0; w < BG_NT / 64; ++w) s += red[w];
-    return s;
-}
 
 // The edgetaper's weights for one kernel (edgetaper.py:10-23): autocorrelations of its two projections at lags 0 .. 48 --
 // what estimate.hip's finish_record keeps for the 25 x 25 record, on the larger grid (an autocorrelation does not care where
@@ -88,7 +78,7 @@ __global__ __launch_bounds__(BG_NT) void big_taps_kernel(const pb_blur_info *inf
         out[idx] = e;
         part += e;
     }
-    const float total = big_block_sum(part, red);
+    const float total = pb_block_sum<float, BG_NT>(part, red);
     for (int idx = threadIdx.x; idx < BK_ROWS * BK_P; idx += BG_NT) out[idx] = out[idx] / total;     // (each thread its own entries)
     big_autocorr(out, acorr + (long)blockIdx.x * 2 * BK_AC);
 }

@@ -44,31 +44,6 @@ __device__ __forceinline__ float taper_weight(const float *ac, int p, int n) {
     return 1.f - z * __frcp_rn(ac[0]);
 }
 
-template <typename T> __device__ __forceinline__ float4 ld4(const T *p);
-template <> __device__ __forceinline__ float4 ld4<float>(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-template <> __device__ __forceinline__ float4 ld4<__half>(const __half *p) {
-    const uint2 u = *reinterpret_cast<const uint2 *>(p);
-    const __half2 a = *reinterpret_cast<const __half2 *>(&u.x), b = *reinterpret_cast<const __half2 *>(&u.y);
-    const float2 fa = __half22float2(a), fb = __half22float2(b);
-    return make_float4(fa.x, fa.y, fb.x, fb.y);
-}
-template <> __device__ __forceinline__ float4 ld4<unsigned char>(const unsigned char *p) {
-    const unsigned u = *reinterpret_cast<const unsigned *>(p);
-    return make_float4(pb_from_ubyte(u & 255u), pb_from_ubyte((u >> 8) & 255u), pb_from_ubyte((u >> 16) & 255u), pb_from_ubyte(u >> 24));
-}
-template <typename T> __device__ __forceinline__ void st4(T *p, float4 v);
-template <> __device__ __forceinline__ void st4<unsigned char>(unsigned char *p, float4 v) {
-    *reinterpret_cast<unsigned *>(p) = pb_to_ubyte(v.x) | (pb_to_ubyte(v.y) << 8) | (pb_to_ubyte(v.z) << 16) | (pb_to_ubyte(v.w) << 24);
-}
-template <> __device__ __forceinline__ void st4<float>(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
-template <> __device__ __forceinline__ void st4<__half>(__half *p, float4 v) {
-    const __half2 a = __floats2half2_rn(v.x, v.y), b = __floats2half2_rn(v.z, v.w);
-    uint2 u;
-    u.x = *reinterpret_cast<const unsigned *>(&a);
-    u.y = *reinterpret_cast<const unsigned *>(&b);
-    *reinterpret_cast<uint2 *>(p) = u;
-}
-
 // Where the outputs of a pass live, in padded coordinates.
 struct OutRegion { int y_lo, y_hi, x_lo, x_hi; };
 __device__ __forceinline__ OutRegion out_region(const ConvPass &a) {
@@ -85,7 +60,7 @@ __device__ __forceinline__ float4 load_x4(const ConvPass &a, const TX *xpl, int 
     const int xc0 = (a.x_kind == SRC_VIRTUAL) ? px - a.pad : px;
     const int xcmax = (a.x_kind == SRC_VIRTUAL) ? W : W + 2 * a.pad;
     const TX *xrow = xpl + (long)xr * a.x_pitch;
-    if (xc0 >= 0 && xc0 + 3 < xcmax && ((a.x_pitch | xc0) & 3) == 0) return ld4<TX>(xrow + xc0);
+    if (xc0 >= 0 && xc0 + 3 < xcmax && ((a.x_pitch | xc0) & 3) == 0) return pb_ld4<TX>(xrow + xc0);
     float4 t;
     t.x = pb_ld(xrow + min(max(xc0, 0), xcmax - 1));
     t.y = pb_ld(xrow + min(max(xc0 + 1, 0), xcmax - 1));
@@ -121,7 +96,7 @@ __device__ __forceinline__ void finish4(const ConvPass &a, const pb_blur_info *i
     const int oc0 = (a.out_kind == OUT_INTERIOR) ? px - a.pad : px;
     TOut *orow_p = opl + (long)orow * a.out_pitch;
     if (full && ((a.out_pitch | oc0) & 3) == 0) {
-        st4<TOut>(orow_p + oc0, make_float4(av[0], av[1], av[2], av[3]));
+        pb_st4<TOut>(orow_p + oc0, make_float4(av[0], av[1], av[2], av[3]));
     } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i)

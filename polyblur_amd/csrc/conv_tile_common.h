@@ -41,7 +41,7 @@ __device__ __forceinline__ float4 load_chunk_mapped(const T *plane, int pitch, i
     const T *row = plane + (long)iy * pitch;
     const int shift = (kind == SRC_VIRTUAL) ? pad : 0;
     const int lo = shift, hi = (kind == SRC_VIRTUAL) ? pad + W : W + 2 * pad;
-    if (aligned && px >= lo && px + 3 < hi) return ld4<T>(row + (px - shift));
+    if (aligned && px >= lo && px + 3 < hi) return pb_ld4<T>(row + (px - shift));
     const int i0 = map_axis(px, W, kind, boundary, pad), i1 = map_axis(px + 1, W, kind, boundary, pad);
     const int i2 = map_axis(px + 2, W, kind, boundary, pad), i3 = map_axis(px + 3, W, kind, boundary, pad);
     if (i0 >= 0) v.x = pb_ld(row + i0);
@@ -90,7 +90,7 @@ __device__ __forceinline__ void load_tile(float *s, const T *plane, int kind, in
         for (int k = 0; k < NLD; ++k) {
             const int e = tid + k * NT;
             const int r = e / C4, c = e - r * C4;
-            if (e < LH * C4) buf[k] = ld4<T>(base + (long)r * pitch + 4 * c);
+            if (e < LH * C4) buf[k] = pb_ld4<T>(base + (long)r * pitch + 4 * c);
         }
 #pragma unroll
         for (int k = 0; k < NLD; ++k) {
@@ -165,7 +165,7 @@ __device__ __forceinline__ void load_rows_wave(float *s, const T *plane, int kin
         for (int k = 0; k < NLD; ++k) {
             const int e = lane + k * 64;
             const int r = e / C4, c = e - r * C4;
-            if (r < nrows) buf[k] = ld4<T>(base + (long)r * pitch + 4 * c);
+            if (r < nrows) buf[k] = pb_ld4<T>(base + (long)r * pitch + 4 * c);
         }
 #pragma unroll
         for (int k = 0; k < NLD; ++k) {
@@ -211,7 +211,7 @@ template <typename TX, typename TOut> struct Block4x4Epilogue {
             xp = xpl + (long)(py - xo) * a.x_pitch + (px - xo);
             op = opl + (long)(py - oo) * a.out_pitch + (px - oo);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) xr[r] = ld4<TX>(xp + (long)r * a.x_pitch);
+            for (int r = 0; r < 4; ++r) xr[r] = pb_ld4<TX>(xp + (long)r * a.x_pitch);
         } else {
             // border blocks: the (clamped) x operand is fetched up front all the same, one row at a time
 #pragma unroll
@@ -235,7 +235,7 @@ template <typename TX, typename TOut> struct Block4x4Epilogue {
                     v.x = fminf(fmaxf(v.x, 0.f), 1.f); v.y = fminf(fmaxf(v.y, 0.f), 1.f);
                     v.z = fminf(fmaxf(v.z, 0.f), 1.f); v.w = fminf(fmaxf(v.w, 0.f), 1.f);
                 }
-                st4<TOut>(op + (long)r * a.out_pitch, v);
+                pb_st4<TOut>(op + (long)r * a.out_pitch, v);
             }
         } else {
             // (statically indexed: a run-time index would push acc[] -- and a 64-byte store per thread -- to scratch)

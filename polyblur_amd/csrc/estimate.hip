@@ -135,7 +135,6 @@ template <typename T> static T *upload(pb_ctx *ctx, const std::vector<T> &h) {
 // The spectral derivative keeps whole lines in LDS (160 KB): lengths up to 20480 when every prime factor is <= 7,
 // up to 8192 otherwise (Bluestein with a power-of-two core of at least 2n-1 points) -> 1.  Longer lines, up to 65536
 // samples, take the same stages on a line buffer in global memory (grad_*_long_kernel) -> 2.  Beyond that -> 0.
-constexpr int kMaxLineLength = 65536;
 extern "C" int pb_fft_length_supported(int n) {
     if (n < 2 || n > kMaxLineLength) return 0;
     std::vector<int> radix;
@@ -273,18 +272,6 @@ using pbfft::dev_plan;
 // ------------------------------------------------------------------------------------
 // gray + min/max
 // ------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ float4 ld4e(const T *p);
-template <> __device__ __forceinline__ float4 ld4e<float>(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-template <> __device__ __forceinline__ float4 ld4e<__half>(const __half *p) {
-    const uint2 u = *reinterpret_cast<const uint2 *>(p);
-    const float2 a = __half22float2(*reinterpret_cast<const __half2 *>(&u.x)), b = __half22float2(*reinterpret_cast<const __half2 *>(&u.y));
-    return make_float4(a.x, a.y, b.x, b.y);
-}
-template <> __device__ __forceinline__ float4 ld4e<unsigned char>(const unsigned char *p) {
-    const unsigned u = *reinterpret_cast<const unsigned *>(p);
-    return make_float4(pb_from_ubyte(u & 255u), pb_from_ubyte((u >> 8) & 255u), pb_from_ubyte((u >> 16) & 255u), pb_from_ubyte(u >> 24));
-}
-
 // VEC: HW % 4 == 0, so every plane starts 16-byte aligned and the image is walked in float4 units.
 // CC: compile-time channel count (1 or 3; 0 = run-time C) so that all channel loads of a sample
 // group are independent and in flight together.
@@ -301,20 +288,17 @@ __global__ __launch_bounds__(NT) void gray_minmax_kernel(const T *__restrict__ i
     if (VEC) {
         const long n4 = HW >> 2;
         for (long i = (long)blk * NT + threadIdx.x; i < n4; i += (long)blocks_per_image * NT) {
-            float4 s4 = ld4e<T>(src + 4 * i);
+            float4 s4 = pb_ld4<T>(src + 4 * i);
             if (CC == 3) {
-                const float4 t1 = ld4e<T>(src + HW + 4 * i), t2 = ld4e<T>(src + 2 * HW + 4 * i);
+                const float4 t1 = pb_ld4<T>(src + HW + 4 * i), t2 = pb_ld4<T>(src + 2 * HW + 4 * i);
                 s4.x = s4.x + t1.x + t2.x; s4.y = s4.y + t1.y + t2.y; s4.z = s4.z + t1.z + t2.z; s4.w = s4.w + t1.w + t2.w;
             } else {
                 for (int c = 1; c < C; ++c) {
-                    const float4 t = ld4e<T>(src + c * HW + 4 * i);
+                    const float4 t = pb_ld4<T>(src + c * HW + 4 * i);
                     s4.x += t.x; s4.y += t.y; s4.z += t.z; s4.w += t.w;
                 }
             }
-            float4 g;
-            if (C == 1) g = s4;
-            else if (C == 3) g = make_float4(s4.x / 3.0f, s4.y / 3.0f, s4.z / 3.0f, s4.w / 3.0f);
-            else g = make_float4(s4.x * invc, s4.y * invc, s4.z * invc, s4.w * invc);
+            const float4 g = pb_gray_of(s4, C, invc);
             *reinterpret_cast<float4 *>(dst + 4 * i) = g;
             lo = fminf(fminf(lo, fminf(g.x, g.y)), fminf(g.z, g.w));
             hi = fmaxf(fmaxf(hi, fmaxf(g.x, g.y)), fmaxf(g.z, g.w));
@@ -323,17 +307,13 @@ __global__ __launch_bounds__(NT) void gray_minmax_kernel(const T *__restrict__ i
         for (long i = (long)blk * NT + threadIdx.x; i < HW; i += (long)blocks_per_image * NT) {
             float s = pb_ld(src + i);
             for (int c = 1; c < C; ++c) s += pb_ld(src + c * HW + i);
-            const float g = (C == 1) ? s : ((C == 3) ? s / 3.0f : s * invc);
+            const float g = pb_gray_of(s, C, invc);
             dst[i] = g;
             lo = fminf(lo, g);
             hi = fmaxf(hi, g);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, o));
-        hi = fmaxf(hi, __shfl_xor(hi, o));
-    }
+    pb_wave_minmax(lo, hi);
     __shared__ float slo[NT / 64], shi[NT / 64];
     if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
     __syncthreads();
@@ -354,11 +334,7 @@ __global__ __launch_bounds__(NT) void minmax_reduce_kernel(const float2 *__restr
         lo = fminf(lo, p.x);
         hi = fmaxf(hi, p.y);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, o));
-        hi = fmaxf(hi, __shfl_xor(hi, o));
-    }
+    pb_wave_minmax(lo, hi);
     __shared__ float slo[NT / 64], shi[NT / 64];
     if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
     __syncthreads();
@@ -600,7 +576,7 @@ __global__ __launch_bounds__(NTH, (NTH == 256 && FUSED) ? 5 : 1) void grad_rows_
 
 // ------------------------------------------------------------------------------------
 // gray + its range + the row transform in ONE pass (q == 0, lines that take the fused transform): the first stage's loads
-// read the image's channels, form the gray samples exactly as gray_minmax_kernel does (blur_estimation.py:36), store them
+// read the image's channels, form the gray samples as gray_minmax_kernel does (pb_gray_of, stage_math.h; blur_estimation.py:36), store them
 // for the column pass and fold them into the workgroup's (min, max) partial -- the gray plane is written once and read
 // once instead of written once and read twice, and one launch of a whole-image pass goes away.
 // ------------------------------------------------------------------------------------
@@ -625,8 +601,7 @@ template <typename T, int CC> struct GrayRowsIO {
                 if (has1) b += pb_ld(row0 + c * cstride + W + p);
             }
         }
-        if (nc == 3) { a = a / 3.0f; b = b / 3.0f; }
-        else if (nc != 1) { a *= invc; b *= invc; }
+        pb_gray_of(a, b, nc, invc);
         g0[p] = a;
         lo = fminf(lo, a); hi = fmaxf(hi, a);
         if (has1) { g0[W + p] = b; lo = fminf(lo, b); hi = fmaxf(hi, b); }
@@ -656,11 +631,7 @@ __global__ __launch_bounds__(NTH, NTH == 256 ? 5 : 1) void gray_rows_kernel(cons
     io.lo = INFINITY; io.hi = -INFINITY;
     pbfft::spectral_derivative_fused<(NTH == 512 ? 24 : 16)>(sfft, plan, 0, io);
     float lo = io.lo, hi = io.hi;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, o));
-        hi = fmaxf(hi, __shfl_xor(hi, o));
-    }
+    pb_wave_minmax(lo, hi);
     __syncthreads();                                               // (the transform's last reads of sfft)
     float *red = reinterpret_cast<float *>(sfft);
     if ((threadIdx.x & 63) == 0) { red[2 * (threadIdx.x >> 6)] = lo; red[2 * (threadIdx.x >> 6) + 1] = hi; }
@@ -696,11 +667,6 @@ __device__ __forceinline__ void reduce_maxima(const float (&best)[PB_MAX_ANGLES]
     }
 }
 
-// cos / sin of the n_angles + 1 directions k pi / n_angles (blur_estimation.py:129-131), evaluated once on the host
-struct AngleTable {
-    float cs[PB_MAX_ANGLES], sn[PB_MAX_ANGLES];
-};
-
 // how the fused transform reaches the 2*nb columns of a workgroup.  MODE 0 writes gy; MODE 1 folds every output
 // sample, with the gx of the same position, into the directional maxima (NA > 0: n_angles + 1 at compile time).
 template <int MODE, int NA> struct ColsIO {
@@ -710,7 +676,7 @@ template <int MODE, int NA> struct ColsIO {
     int W, c0, na;
     bool vec2, discard_sat, normalize;
     float lo, scale, inv, sat_threshold;
-    AngleTable ang;
+    PbAngleTable ang;
     float best[PB_MAX_ANGLES];
     __device__ __forceinline__ float2 load(int p, int j) const {
         const int c = c0 + 2 * j;
@@ -768,7 +734,7 @@ __global__ __launch_bounds__(NTH) void grad_cols_kernel(const float *__restrict_
                                                        const unsigned *__restrict__ mm, int planes_per_image,
                                                        unsigned *__restrict__ mags, int n_angles, int discard_sat,
                                                        float sat_threshold, int total_tiles, pbfft::DevPlan plan,
-                                                       AngleTable ang) {
+                                                       PbAngleTable ang) {
     extern __shared__ __attribute__((aligned(16))) float2 sfft[];
     const int nb = 1 << lognb;
     const int tc = 2 * nb;
@@ -952,7 +918,7 @@ __global__ __launch_bounds__(LONG_NT) void grad_cols_long_kernel(const float *__
                                                                 const unsigned *__restrict__ mm, int planes_per_image,
                                                                 unsigned *__restrict__ mags, int n_angles, int discard_sat,
                                                                 float sat_threshold, int total_tiles, pbfft::DevPlan plan,
-                                                                AngleTable ang, float2 *scratch) {
+                                                                PbAngleTable ang, float2 *scratch) {
     __shared__ float red[LONG_NT / 64 * PB_MAX_ANGLES];
     float2 *s = scratch + (size_t)blockIdx.x * ((size_t)plan.n << lognb);
     const int nb = 1 << lognb;
@@ -1024,17 +990,6 @@ __global__ __launch_bounds__(LONG_NT) void grad_cols_long_kernel(const float *__
 // ------------------------------------------------------------------------------------
 // parameters and kernels
 // ------------------------------------------------------------------------------------
-__device__ float block_sum(float v, float *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int w = 0; w < NT / 64; ++w) s += red[w];
-    return s;
-}
-
 // The ker_size x ker_size Gaussian of (theta, sigma, rho) in the 25 x 25 record (blur_estimation.py:189-232), normalised:
 // into sk (LDS) and, where given, into the record's taps in global memory.  Called by all NT threads of a block (barriers
 // inside; sk is NOT yet visible to the other threads on return).
@@ -1068,7 +1023,7 @@ __device__ __forceinline__ void gaussian_taps(float *sk, float *gk, float theta,
             part += e[q];
         }
     }
-    const float total = block_sum(part, red);
+    const float total = pb_block_sum<float, NT>(part, red);
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
         const int idx = tid + q * NT;
@@ -1149,7 +1104,7 @@ __device__ void finish_record(pb_blur_info *info, int support, bool from_taps, f
     for (int idx = tid; idx < PB_KSIZE * PB_KSIZE; idx += NT)
         res += fabsf(sk[idx] - sky[idx / PB_KSIZE] * skx[idx % PB_KSIZE]);
     PB_PT(6);
-    const float resid = block_sum(res, red);
+    const float resid = pb_block_sum<float, NT>(res, red);
     PB_PT(7);
     // FULL: every tap that is not exactly 0.0f is evaluated (rows / columns whose taps all underflowed to
     // zero -- sigma below ~0.9 -- are skipped: bit-identical to evaluating them).  ADAPTIVE: the smallest
@@ -1313,11 +1268,7 @@ __global__ __launch_bounds__(NT) void blur_params_kernel(pb_blur_info *infos, co
         for (int o = 8; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
         s_part[threadIdx.x] = m;
         if (part) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                plo = fminf(plo, __shfl_xor(plo, o));
-                phi = fmaxf(phi, __shfl_xor(phi, o));
-            }
+            pb_wave_minmax(plo, phi);
             if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = plo; s_hi[threadIdx.x >> 6] = phi; }
         }
         __syncthreads();
@@ -1364,19 +1315,13 @@ __global__ __launch_bounds__(NT) void blur_params_kernel(pb_blur_info *infos, co
             if (ov < vmin || (ov == vmin && oi < i_min)) { vmin = ov; i_min = oi; }
         }
         if (lane == 0) {
-            const float step = 180.0f / (float)n_interp;
-            int theta_deg = (int)((float)i_min * step);            // interpolated_thetas.long()
-            if (force_theta_deg >= 0.f) {
-                theta_deg = (int)force_theta_deg;
-                i_min = (int)((float)theta_deg / step);
-                vmin = s_interp[i_min];
-            }
-            const int ortho_deg = (theta_deg + 90) % 180;
-            const int i_ortho = (int)((float)ortho_deg / step);
+            int theta_deg, i_ortho;
+            pb_interp_pair(i_min, n_interp, force_theta_deg, &theta_deg, &i_min, &i_ortho);
+            if (force_theta_deg >= 0.f) vmin = s_interp[i_min];
             const float m_n = vmin, m_o = s_interp[i_ortho];
             const float cc = c * c, bb = b * b;
-            s_par[1] = sqrtf(fminf(fmaxf(cc / (m_n * m_n + 1e-8f) - bb, 0.09f), 16.0f));
-            s_par[2] = sqrtf(fminf(fmaxf(cc / (m_o * m_o + 1e-8f) - bb, 0.09f), 16.0f));
+            s_par[1] = pb_sigma_of(pb_variance_of(m_n, cc, bb));
+            s_par[2] = pb_sigma_of(pb_variance_of(m_o, cc, bb));
             s_par[0] = (float)theta_deg * 3.14159274101257324f / 180.0f;
             if (rec_wg) {
                 info->theta = s_par[0];
@@ -1732,12 +1677,8 @@ int launch_cols(pb_ctx *ctx, const float *planes, const float *gx, float *gy, in
     if (blocks > 0x7fffffffL) return pb_fail(ctx, PB_ERR_BADARG, "column transform: bad grid");
     const pbfft::DevPlan dp = dev_plan(pl);
     const float thr = 0.99f;
-    AngleTable ang;
-    for (int k = 0; k < PB_MAX_ANGLES; ++k) {
-        const float t = n_angles > 0 ? 3.14159265358979323846f * (float)k / (float)n_angles : 0.f;
-        ang.cs[k] = std::cos(t);
-        ang.sn[k] = std::sin(t);
-    }
+    PbAngleTable ang;
+    pb_angle_table(n_angles, ang.cs, ang.sn, PB_MAX_ANGLES);
     if (through_memory) {                           // as launch_rows: a slot of 2 << lognb columns per workgroup
         const long grid = long_grid(blocks, lds);
         float2 *slots = static_cast<float2 *>(pb_scratch(ctx, "fft.long", (size_t)grid * lds));

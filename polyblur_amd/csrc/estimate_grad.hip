@@ -4,7 +4,7 @@
 // directional maxima (torch.amax: to the arg-max pixel) <- the spectral derivative <- the range normalisation <- the channel
 // mean; here five launches do:
 //
-//   est_gray_extrema   the gray plane (the forward's arithmetic, so that == gray_min / gray_max means what it meant there)
+//   est_gray_extrema   the gray plane (pb_gray_of, the forward's own, so that == gray_min / gray_max means what it meant there)
 //                      and, per workgroup, how many samples sit at either end of the range
 //   (the forward's spectral-derivative launchers: gradient planes of the gray image -- the arg-max of |proj| and its sign
 //    do not depend on the positive factor 1 / (hi - lo))
@@ -15,21 +15,18 @@
 //   est_grad_scatter   every output sample sums its row and column terms with the impulse response of the spectral
 //                      derivative in closed form, adds its share of d lo / d hi, divides by C
 //
+// The formulas this file shares with the forward are the forward's own definitions (stage_math.h).
 // The forward's decisions (i_min, theta, gray_min, gray_max, the clamps' state) come from its record; the arg-max pixels are found
 // again, and the magnitudes, sigma and rho are evaluated again at those pixels in double (est_param_grad says why).  Sums in a
 // fixed order, no float atomics: the same call gives the same bits.
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
+#include "stage_math.h"
 
 namespace {
 
 constexpr int EG_NT = 256;
-
-struct EgAngles {
-    float cs[PB_MAX_ANGLES], sn[PB_MAX_ANGLES];
-};
 
 // what est_param_grad leaves for the scatter, per image
 struct EgCoef {
@@ -46,18 +43,6 @@ struct EgSel {
 __device__ __forceinline__ bool eg_better(float av, int ai, float bv, int bi) {   // is (bv, bi) ahead of (av, ai)?
     const float a = fabsf(av), b = fabsf(bv);
     return b > a || (b == a && bi < ai);
-}
-
-// sum over the workgroup, the same order whatever the data: lanes by xor shuffles, waves in index order
-template <typename T> __device__ __forceinline__ T eg_block_sum(T v, T *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T s = 0;
-    for (int w = 0; w < EG_NT / 64; ++w) s += red[w];
-    return s;
 }
 
 // impulse response of the spectral derivative along an axis of N samples (filters.py:172-184): out[j] = sum_m in[m] d[(j - m) mod N]
@@ -86,7 +71,7 @@ __device__ __forceinline__ double eg_deriv_d(int n, int N) {                    
 __device__ __forceinline__ float eg_gray(const float *src, long HW, long i, int C, float invc) {
     float s = src[i];
     for (int c = 1; c < C; ++c) s += src[c * HW + i];
-    return (C == 1) ? s : ((C == 3) ? s / 3.0f : s * invc);   // (gray_minmax_kernel / GrayRowsIO, estimate.hip)
+    return pb_gray_of(s, C, invc);
 }
 
 __global__ __launch_bounds__(EG_NT) void est_gray_extrema(const float *__restrict__ in, const pb_blur_info *__restrict__ infos,
@@ -102,8 +87,7 @@ __global__ __launch_bounds__(EG_NT) void est_gray_extrema(const float *__restric
         nlo += g == lo ? 1u : 0u;
         nhi += g == hi ? 1u : 0u;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { nlo += __shfl_xor(nlo, o); nhi += __shfl_xor(nhi, o); }
+    nlo = pb_wave_sum(nlo); nhi = pb_wave_sum(nhi);
     __shared__ unsigned slo[EG_NT / 64], shi[EG_NT / 64];
     if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = nlo; shi[threadIdx.x >> 6] = nhi; }
     __syncthreads();
@@ -117,7 +101,7 @@ __global__ __launch_bounds__(EG_NT) void est_gray_extrema(const float *__restric
 template <bool VEC>
 __global__ __launch_bounds__(EG_NT) void est_dir_argmax(const float *__restrict__ gx, const float *__restrict__ gy, const float *__restrict__ gray,
                                                         EgSel *__restrict__ part, long HW, int bpi, int na, int discard_sat, float thr,
-                                                        EgAngles ang) {
+                                                        PbAngleTable ang) {
     const int b = blockIdx.y, blk = blockIdx.x;
     const float *px = gx + (long)b * HW, *py = gy + (long)b * HW, *pg = gray + (long)b * HW;
     float bv[PB_MAX_ANGLES];
@@ -129,7 +113,7 @@ __global__ __launch_bounds__(EG_NT) void est_dir_argmax(const float *__restrict_
 #pragma unroll
         for (int k = 0; k < PB_MAX_ANGLES; ++k) {
             if (k < na) {
-                const float p = fmaf(ang.cs[k], dx, -__fmul_rn(ang.sn[k], dy));     // (pbfft::dir_abs, fft.h)
+                const float p = pb_dir_proj(ang.cs[k], ang.sn[k], dx, dy);
                 if (fabsf(p) > fabsf(bv[k]) || (bi[k] == 0x7fffffff && p == p)) { bv[k] = p; bi[k] = idx; }
             }
         }
@@ -211,7 +195,7 @@ __global__ __launch_bounds__(EG_NT) void est_param_grad(const pb_blur_info *__re
                                                         const EgSel *__restrict__ sel, const float *__restrict__ gray,
                                                         const uint2 *__restrict__ counts, EgCoef *__restrict__ coefs, int H, int W,
                                                         int bpi_counts, int n_angles, int n_interp, float c, float bq, int ksize,
-                                                        EgAngles ang) {
+                                                        PbAngleTable ang) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const pb_blur_info *info = infos + b;
     const int na = n_angles + 1;
@@ -246,8 +230,8 @@ __global__ __launch_bounds__(EG_NT) void est_param_grad(const pb_blur_info *__re
             for (int m = tid; m < W; m += EG_NT) { int n = ja - m; if (n < 0) n += W; sx += eg_deriv_d(n, W) * (double)g[(long)ia * W + m]; }
             for (int m = tid; m < H; m += EG_NT) { int n = ia - m; if (n < 0) n += H; sy += eg_deriv_d(n, H) * (double)g[(long)m * W + ja]; }
         }
-        sx = eg_block_sum(sx, redd);
-        sy = eg_block_sum(sy, redd);
+        sx = pb_block_sum<double, EG_NT>(sx, redd);
+        sy = pb_block_sum<double, EG_NT>(sy, redd);
         if (tid == 0) {
             const double t = 3.14159265358979323846 * (double)k / (double)n_angles;
             const double p = cos(t) * sx - sin(t) * sy;
@@ -256,22 +240,17 @@ __global__ __launch_bounds__(EG_NT) void est_param_grad(const pb_blur_info *__re
         }
     }
     if (tid == 0) {
-        const int i_min = min(max(info->i_min, 0), n_interp - 1);
-        const float step = 180.0f / (float)n_interp;
-        const int theta_deg = (int)((float)i_min * step);
-        s_im[0] = i_min;
-        s_im[1] = (int)((float)((theta_deg + 90) % 180) / step);
+        int theta_deg;
+        pb_interp_pair(min(max(info->i_min, 0), n_interp - 1), n_interp, -1.f, &theta_deg, &s_im[0], &s_im[1]);
         const double cc = (double)c * c, bb = (double)bq * bq;
         for (int e = 0; e < 2; ++e) {
             double m = 0.0;
             for (int k = 0; k < na; ++k) m += (double)wts[s_im[e] * na + k] * s_mag[k];
             // (the clamp's state is the forward's: its own fp32 value of v)
             const float mf = info->interp[s_im[e]];
-            const float vf = c * c / (mf * mf + 1e-8f) - bq * bq;
-            s_pass[e] = (vf >= 0.09f && vf <= 16.0f) ? 1 : 0;
-            const double v = cc / (m * m + 1e-8) - bb;
+            s_pass[e] = pb_variance_passes(pb_variance_of(mf, c * c, bq * bq)) ? 1 : 0;
             s_m[e] = m;
-            s_par[e] = s_pass[e] ? sqrt(fmin(fmax(v, 0.09), 16.0)) : (double)(e == 0 ? info->sigma : info->rho);
+            s_par[e] = s_pass[e] ? pb_sigma_of(pb_variance_of(m, cc, bb)) : (double)(e == 0 ? info->sigma : info->rho);
         }
     }
     __syncthreads();
@@ -291,8 +270,8 @@ __global__ __launch_bounds__(EG_NT) void est_param_grad(const pb_blur_info *__re
             const double e = exp(-0.5 * (a00 * X * X + 2.0 * a01 * X * Y + a11 * Y * Y));
             esum += e; dot += (double)gk[i] * e;
         }
-        esum = eg_block_sum(esum, redd);
-        dot = eg_block_sum(dot, redd) / esum;
+        esum = pb_block_sum<double, EG_NT>(esum, redd);
+        dot = pb_block_sum<double, EG_NT>(dot, redd) / esum;
         double sxx = 0.0, sxy = 0.0, syy = 0.0;
         for (int i = tid; i < kk; i += EG_NT) {
             const int iy = i / ksize, ix = i - iy * ksize;
@@ -301,7 +280,7 @@ __global__ __launch_bounds__(EG_NT) void est_param_grad(const pb_blur_info *__re
             const double ge = ((double)gk[i] - dot) * K;
             sxx += ge * X * X; sxy += ge * X * Y; syy += ge * Y * Y;
         }
-        sxx = eg_block_sum(sxx, redd); sxy = eg_block_sum(sxy, redd); syy = eg_block_sum(syy, redd);
+        sxx = pb_block_sum<double, EG_NT>(sxx, redd); sxy = pb_block_sum<double, EG_NT>(sxy, redd); syy = pb_block_sum<double, EG_NT>(syy, redd);
         const double cc = ct * ct, ss = st * st, sc2 = 2.0 * st * ct;
         d_i1 = -0.5 * (cc * sxx + sc2 * sxy + ss * syy);
         d_i2 = -0.5 * (ss * sxx - sc2 * sxy + cc * syy);
@@ -314,7 +293,7 @@ __global__ __launch_bounds__(EG_NT) void est_param_grad(const pb_blur_info *__re
         const double cc = (double)c * c;
         double dm[2];
         for (int e = 0; e < 2; ++e) {
-            const double m = s_m[e], den = m * m + 1e-8;
+            const double m = s_m[e], den = m * m + PbVariance<double>::eps;
             const double dv = s_pass[e] ? dpar[e] / (2.0 * s_par[e]) : 0.0;
             dm[e] = dv * (-2.0 * cc * m) / (den * den);
         }
@@ -333,8 +312,7 @@ __global__ __launch_bounds__(EG_NT) void est_param_grad(const pb_blur_info *__re
     // how many samples sit at either end of the range
     unsigned nlo = 0, nhi = 0;
     for (int i = tid; i < bpi_counts; i += EG_NT) { const uint2 q = counts[(long)b * bpi_counts + i]; nlo += q.x; nhi += q.y; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { nlo += __shfl_xor(nlo, o); nhi += __shfl_xor(nhi, o); }
+    nlo = pb_wave_sum(nlo); nhi = pb_wave_sum(nhi);
     if (tid == 0) { s_cnt[0] = 0u; s_cnt[1] = 0u; }
     __syncthreads();
     if ((tid & 63) == 0) { atomicAdd(&s_cnt[0], nlo); atomicAdd(&s_cnt[1], nhi); }       // (integers: any order, one sum)
@@ -361,8 +339,8 @@ __global__ __launch_bounds__(EG_NT) void est_param_grad(const pb_blur_info *__re
         }
         t_lo = fmaf(cy, a_lo, t_lo); t_hi = fmaf(cy, a_hi, t_hi);
     }
-    t_lo = eg_block_sum(t_lo, red);
-    t_hi = eg_block_sum(t_hi, red);
+    t_lo = pb_block_sum<float, EG_NT>(t_lo, red);
+    t_hi = pb_block_sum<float, EG_NT>(t_hi, red);
     if (tid == 0) {
         const float inv = hi > lo ? 1.f / (hi - lo) : 0.f;
         sc.lo_share = s_cnt[0] ? t_lo * inv / (float)s_cnt[0] : 0.f;
@@ -424,7 +402,7 @@ extern "C" int pb_estimate_blur_backward(pb_ctx *ctx, const float *in, int B, in
     const long HW = (long)H * W;
     if (HW > 0x7fffffffL - 4) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "pb_estimate_blur_backward: planes of up to 2^31 samples");
     if (!pb_fft_length_supported(H) || !pb_fft_length_supported(W))
-        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "image %d x %d: lines of up to 65536 samples are supported", H, W);
+        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "image %d x %d: lines of up to %d samples are supported", H, W, kMaxLineLength);
     PB_HIP(hipSetDevice(ctx->device));
     const int na = opt->n_angles + 1;
     const int bpi = eg_blocks(HW, B);
@@ -443,12 +421,8 @@ extern "C" int pb_estimate_blur_backward(pb_ctx *ctx, const float *in, int B, in
     uint2 *counts = reinterpret_cast<uint2 *>(coefs + B);
     const float *wts = pb_get_interp_weights(ctx, opt->n_angles, opt->n_interpolated_angles);
     if (!wts) return PB_ERR_NOMEM;
-    EgAngles ang;
-    for (int k = 0; k < PB_MAX_ANGLES; ++k) {                     // (launch_cols, estimate.hip)
-        const float t = 3.14159265358979323846f * (float)k / (float)opt->n_angles;
-        ang.cs[k] = std::cos(t);
-        ang.sn[k] = std::sin(t);
-    }
+    PbAngleTable ang;
+    pb_angle_table(opt->n_angles, ang.cs, ang.sn, PB_MAX_ANGLES);
     {
         ProfScope prof(ctx, PB_PROF_OTHER);
         hipLaunchKernelGGL(est_gray_extrema, dim3(bpi, B), dim3(EG_NT), 0, ctx->stream, in, dev_info, gray, counts, C, HW, bpi);

@@ -23,7 +23,7 @@
 // that saves a stage (4320 = 18 x 16 x 15, 7680 = 24 x 20 x 16: the 8K sides); any other length
 // goes through Bluestein's chirp-z with a power-of-two inner length (plan.bluestein_m).
 #pragma once
-#include "common.h"
+#include "stage_math.h"
 
 // (lab builds: PB_FT(i) stamps the stages of spectral_derivative_fused -- estimate.hip defines it under
 // -DPB_EXPERIMENTAL -DPB_LINES_TRACE, tools/lines_trace.py reads the stamps)
@@ -161,9 +161,8 @@ template <> __device__ __forceinline__ void dft_small<7>(cf (&v)[7]) {        //
     for (int k = 0; k < 7; ++k) v[k] = o[k];
 }
 
-// |cos(t) gx - sin(t) gy| of the directional maxima (blur_estimation.py:129-133) with its roundings written out (as above: the
-// second product rounded, the first fused into the difference), so that every kernel that folds a sample gets the same bits
-__device__ __forceinline__ float dir_abs(float cs, float sn, float dx, float dy) { return fabsf(fmaf(cs, dx, -__fmul_rn(sn, dy))); }
+// |cos(t) gx - sin(t) gy| of the directional maxima (blur_estimation.py:129-133): every kernel that folds a sample gets the same bits
+__device__ __forceinline__ float dir_abs(float cs, float sn, float dx, float dy) { return fabsf(pb_dir_proj(cs, sn, dx, dy)); }
 
 // ---- composite radices, evaluated in registers as A x B Cooley-Tukey with constant twiddles -------------
 // X[k1 + A k2] = sum_{n2} W_N^{n2 k1} ( sum_{n1} x[n1 B + n2] W_A^{n1 k1} ) W_B^{n2 k2},  N = A B

@@ -3,7 +3,7 @@
 //   domain-transform recursive filter domain_transform.py:6-85, native twin RF.cpp:14-92
 //   5x5 bilateral filter             filters.py:107-148
 //   prefilter recombination          deblurring.py:84,88
-#include "common.h"
+#include "stage_math.h"
 
 int pb_fourier_gradients_impl(pb_ctx *ctx, const float *planes, int P, int H, int W, float *gx, float *gy);
 
@@ -17,7 +17,6 @@ constexpr int NT = 256;
 // nM[plane] = sum_{H,W} gx^2 + gy^2          (deblurring.py:178-179,206)
 // VEC: planes of whole groups of four samples on 16-byte (fp16: 8-byte) boundaries -- four samples per lane and trip (round 6:
 // 78 -> 45 us on a 4K image's three planes); which samples a lane sums, and in which order, depends on the plane's size alone.
-template <typename T> __device__ __forceinline__ float4 ld4v(const T *p);
 template <typename TG, bool VEC>
 __global__ __launch_bounds__(NT) void grad_energy_kernel(const TG *__restrict__ gx, const TG *__restrict__ gy,
                                                          float *__restrict__ partial, long HW, int blocks_per_plane) {
@@ -27,7 +26,7 @@ __global__ __launch_bounds__(NT) void grad_energy_kernel(const TG *__restrict__ 
     float s = 0.f;
     if constexpr (VEC) {
         for (long i = 4 * ((long)blk * NT + threadIdx.x); i < HW; i += 4l * blocks_per_plane * NT) {
-            const float4 u = ld4v(a + i), v = ld4v(b + i);
+            const float4 u = pb_ld4(a + i), v = pb_ld4(b + i);
             s += u.x * u.x + v.x * v.x;
             s += u.y * u.y + v.y * v.y;
             s += u.z * u.z + v.z * v.z;
@@ -39,51 +38,17 @@ __global__ __launch_bounds__(NT) void grad_energy_kernel(const TG *__restrict__ 
             s += u * u + v * v;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     __shared__ float red[NT / 64];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int w = 0; w < NT / 64; ++w) t += red[w];
-        partial[blockIdx.x] = t;
-    }
-}
-// one wave per plane folds that plane's per-block partial sums in a fixed order: nM is bit-reproducible
-__global__ __launch_bounds__(64) void grad_energy_fold_kernel(const float *__restrict__ partial, float *__restrict__ nM,
-                                                              int blocks_per_plane) {
-    const float *p = partial + (long)blockIdx.x * blocks_per_plane;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < blocks_per_plane; i += 64) s += p[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (threadIdx.x == 0) nM[blockIdx.x] = s;
+    const float t = pb_block_sum_to_first<NT>(s, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = t;       // (folded per plane by pb_fold_partials_kernel: nM is bit-reproducible)
 }
 
-// M = -gx*ox - gy*gy  (sic: deblurring.py:174 multiplies grad_y by itself, not by gout_y)
-// z = max(M / (nM + M), 0);  out = y + z (x - y)   [+ clamp to [0,1], deblurring.py:239]
+// z = max(M / (nM + M), 0), M = -gx*ox - gy*gy (sic) -- pb_halo_ratio, stage_math.h;  out = y + z (x - y)   [+ clamp to [0,1], deblurring.py:239]
 // With a prefilter the masked result is recombined on the spot (cur != nullptr; recombine_kernel's arithmetic):
 // out = clip(clip(out, 0, 1) + (cur - smooth), 0, 1) -- one pass over the batch instead of a store, a load and a pass.
 // TG: the type the three gradient planes are kept in -- fp32, or fp16 where the call's images are fp16 (z = M / (nM + M) is a
 // ratio of one sample's products to the whole plane's energy, ~1e-5 on an image: an fp16 rounding of its factors moves the
 // output by ~1e-9, and the three planes are 12 of the 28 bytes this kernel moves per sample)
-// four consecutive samples of a plane as floats (16 bytes of fp32, 8 of fp16): the streaming kernels' unit where rows allow it
-template <> __device__ __forceinline__ float4 ld4v<float>(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-template <> __device__ __forceinline__ float4 ld4v<__half>(const __half *p) {
-    const uint2 u = *reinterpret_cast<const uint2 *>(p);
-    const float2 a = __half22float2(*reinterpret_cast<const __half2 *>(&u.x)), b = __half22float2(*reinterpret_cast<const __half2 *>(&u.y));
-    return make_float4(a.x, a.y, b.x, b.y);
-}
-template <typename T> __device__ __forceinline__ void st4v(T *p, float4 v);
-template <> __device__ __forceinline__ void st4v<float>(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
-template <> __device__ __forceinline__ void st4v<__half>(__half *p, float4 v) {
-    const __half2 a = __floats2half2_rn(v.x, v.y), b = __floats2half2_rn(v.z, v.w);
-    uint2 u;
-    u.x = *reinterpret_cast<const unsigned *>(&a); u.y = *reinterpret_cast<const unsigned *>(&b);
-    *reinterpret_cast<uint2 *>(p) = u;
-}
-
 // VEC: every plane's rows start on a boundary of four samples (W, the x operand's pitch and plane stride multiples of 4): four
 // samples per thread and trip -- the same operations per sample, 16-byte (fp16: 8-byte) accesses, no 64-bit division per sample
 template <typename TX, typename TOut, typename TG, bool VEC>
@@ -102,12 +67,12 @@ __global__ __launch_bounds__(NT) void halo_kernel(const TX *__restrict__ x, int 
             for (long i4 = (long)blockIdx.x * NT + threadIdx.x; i4 < n4; i4 += (long)gridDim.x * NT) {
                 const int r = (int)((unsigned)i4 / (unsigned)W4), c = 4 * ((int)i4 - r * W4);       // (H W / 4 < 2^32: sides up to 65536)
                 const long k = (long)plane * HW + 4 * i4;
-                const float4 gxx = ld4v(gx + k), gyy = ld4v(gy + k), oxx = ld4v(ox + k), yv = ld4v(y + k);
-                const float4 xv = ld4v(x + (long)plane * x_plane + (long)r * x_pitch + c);
+                const float4 gxx = pb_ld4(gx + k), gyy = pb_ld4(gy + k), oxx = pb_ld4(ox + k), yv = pb_ld4(y + k);
+                const float4 xv = pb_ld4(x + (long)plane * x_plane + (long)r * x_pitch + c);
                 float4 cv = make_float4(0.f, 0.f, 0.f, 0.f), sm = cv;
                 if (cur) {
-                    cv = cur_is_half ? ld4v(static_cast<const __half *>(cur) + k) : ld4v(static_cast<const float *>(cur) + k);
-                    sm = ld4v(smooth + k);
+                    cv = cur_is_half ? pb_ld4(static_cast<const __half *>(cur) + k) : pb_ld4(static_cast<const float *>(cur) + k);
+                    sm = pb_ld4(smooth + k);
                 }
                 const float g1[4] = {gxx.x, gxx.y, gxx.z, gxx.w}, g2[4] = {gyy.x, gyy.y, gyy.z, gyy.w}, o1[4] = {oxx.x, oxx.y, oxx.z, oxx.w};
                 const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ys[4] = {yv.x, yv.y, yv.z, yv.w};
@@ -115,8 +80,7 @@ __global__ __launch_bounds__(NT) void halo_kernel(const TX *__restrict__ x, int 
                 float o[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float M = fmaf(-g1[e], o1[e], -__fmul_rn(g2[e], g2[e]));      // (roundings written out: both forms of the kernel give the same bits)
-                    const float z = fmaxf(M / (nm + M), 0.f);
+                    const float z = pb_halo_ratio(g1[e], g2[e], o1[e], nm).z;
                     float v = fmaf(z, xs[e] - ys[e], ys[e]);
                     if (clamp01) v = fminf(fmaxf(v, 0.f), 1.f);
                     if (cur) {
@@ -126,7 +90,7 @@ __global__ __launch_bounds__(NT) void halo_kernel(const TX *__restrict__ x, int 
                     }
                     o[e] = v;
                 }
-                st4v(out + k, make_float4(o[0], o[1], o[2], o[3]));
+                pb_st4(out + k, make_float4(o[0], o[1], o[2], o[3]));
             }
         }
         return;
@@ -137,8 +101,7 @@ __global__ __launch_bounds__(NT) void halo_kernel(const TX *__restrict__ x, int 
         const int r = (int)(i / W), c = (int)(i - (long)r * W);
         const long k = (long)plane * HW + i;
         const float gxx = pb_ld(gx + k), gyy = pb_ld(gy + k);
-        const float M = fmaf(-gxx, pb_ld(ox + k), -__fmul_rn(gyy, gyy));
-        const float z = fmaxf(M / (nm + M), 0.f);
+        const float z = pb_halo_ratio(gxx, gyy, pb_ld(ox + k), nm).z;
         const float xv = pb_ld(x + (long)plane * x_plane + (long)r * x_pitch + c);
         const float yv = y[k];
         float v = fmaf(z, xv - yv, yv);
@@ -1151,6 +1114,15 @@ unsigned grid_for(long n, int per_block = NT, int cap = 8192) {
 
 }  // namespace
 
+// (common.h) one wave per output folds that output's per-workgroup partial sums in a fixed order
+__global__ __launch_bounds__(64) void pb_fold_partials_kernel(const float *__restrict__ partial, float *__restrict__ out, int per_out) {
+    const float *p = partial + (long)blockIdx.x * per_out;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < per_out; i += 64) s += p[i];
+    s = pb_wave_sum(s);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
 // ---- internal entry points used by api.hip --------------------------------------------------
 int pb_grad_energy(pb_ctx *ctx, const void *gx, const void *gy, float *nM, int P, long HW, int g_dtype) {
     ProfScope prof(ctx, PB_PROF_HALO);
@@ -1166,7 +1138,7 @@ int pb_grad_energy(pb_ctx *ctx, const void *gx, const void *gy, float *nM, int P
     if (g_dtype == PB_F16) { if (vec) PB_GE(__half, true); else PB_GE(__half, false); }
     else { if (vec) PB_GE(float, true); else PB_GE(float, false); }
 #undef PB_GE
-    hipLaunchKernelGGL(grad_energy_fold_kernel, dim3(P), dim3(64), 0, ctx->stream, partial, nM, bpp);
+    hipLaunchKernelGGL(pb_fold_partials_kernel, dim3(P), dim3(64), 0, ctx->stream, partial, nM, bpp);
     PB_LAUNCH_CHECK();
     return PB_OK;
 }

@@ -15,7 +15,7 @@
 //   (the forward's own launchers: nM and ox again, the forward's bits)
 //   halo_grad_pass1    streams the planes once: grad_x, g (1 - z) into grad_y, -ox dM and -2 gy dM into the two grad0 outputs,
 //                      -gx dM into a scratch plane, per workgroup the partial sum of -q M
-//   halo_grad_fold     one wave per plane folds its partials in index order: S
+//   pb_fold_partials_kernel   one wave per plane folds its partials in index order: S
 //   (the forward's row transform on the scratch plane, into the plane that held ox)
 //   halo_grad_finish   grad_y -= T, grad_gx += 2 gx S, grad_gy += 2 gy S
 //
@@ -25,7 +25,7 @@
 #include <cstdint>
 #include <initializer_list>
 
-#include "common.h"
+#include "stage_math.h"
 
 int pb_grad_energy(pb_ctx *ctx, const void *gx, const void *gy, float *nM, int P, long HW, int g_dtype = PB_F32);
 
@@ -37,28 +37,22 @@ struct HgSample {
     float gradx, grady0, ggx0, ggy0, t, s;       // s: -q M
 };
 
-// One sample of pass one.  M, r and z exactly as halo_kernel (filters.hip) evaluates them, so that a sample on the kink is
-// classified as the forward classified it; every rounding written out, so that both forms of the kernel give the same bits.
+// One sample of pass one.  M, r and z are halo_kernel's own (pb_halo_ratio, stage_math.h): a sample on the kink is classified
+// as the forward classified it; every rounding written out, so that both forms of the kernel give the same bits.
 __device__ __forceinline__ HgSample hg_sample(float x, float y, float gx, float gy, float ox, float g, float nm) {
-    const float M = fmaf(-gx, ox, -__fmul_rn(gy, gy));
-    const float den = nm + M;
-    const float r = M / den;
-    const float z = fmaxf(r, 0.f);
+    const PbHalo h = pb_halo_ratio(gx, gy, ox, nm);
     const float dz = __fmul_rn(g, x - y);
-    const float q = r >= 0.f ? dz / __fmul_rn(den, den) : 0.f;
+    const float q = h.r >= 0.f ? dz / __fmul_rn(h.den, h.den) : 0.f;
     const float dM = __fmul_rn(q, nm);
     HgSample o;
-    o.gradx = __fmul_rn(g, z);
+    o.gradx = __fmul_rn(g, h.z);
     o.grady0 = g - o.gradx;
     o.ggx0 = __fmul_rn(-ox, dM);
     o.ggy0 = __fmul_rn(-2.f * gy, dM);
     o.t = __fmul_rn(-gx, dM);
-    o.s = __fmul_rn(-q, M);
+    o.s = __fmul_rn(-q, h.M);
     return o;
 }
-
-__device__ __forceinline__ float4 hg_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void hg_st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
 
 // VEC: planes of whole groups of four samples on 16-byte boundaries.  One workgroup = block `blk` of `bpp` of one plane
 // (blockIdx.x = plane * bpp + blk: the grid's x dimension takes any number of planes).  Outputs that are nullptr are not stored.
@@ -77,18 +71,18 @@ __global__ __launch_bounds__(HG_NT) void halo_grad_pass1(const float *__restrict
     if constexpr (VEC) {
         for (long i = 4 * ((long)blk * HG_NT + threadIdx.x); i < HW; i += 4l * bpp * HG_NT) {
             const long k = base + i;
-            const float4 xv = hg_ld4(x + k), yv = hg_ld4(y + k), av = hg_ld4(gx + k), bv = hg_ld4(gy + k), ov = hg_ld4(ox + k), gv = hg_ld4(g + k);
+            const float4 xv = pb_ld4(x + k), yv = pb_ld4(y + k), av = pb_ld4(gx + k), bv = pb_ld4(gy + k), ov = pb_ld4(ox + k), gv = pb_ld4(g + k);
             const HgSample e0 = hg_sample(xv.x, yv.x, av.x, bv.x, ov.x, gv.x, nm);
             const HgSample e1 = hg_sample(xv.y, yv.y, av.y, bv.y, ov.y, gv.y, nm);
             const HgSample e2 = hg_sample(xv.z, yv.z, av.z, bv.z, ov.z, gv.z, nm);
             const HgSample e3 = hg_sample(xv.w, yv.w, av.w, bv.w, ov.w, gv.w, nm);
-            if (grad_x) hg_st4(grad_x + k, make_float4(e0.gradx, e1.gradx, e2.gradx, e3.gradx));
+            if (grad_x) pb_st4(grad_x + k, make_float4(e0.gradx, e1.gradx, e2.gradx, e3.gradx));
             if (grad_y) {
-                hg_st4(grad_y + k, make_float4(e0.grady0, e1.grady0, e2.grady0, e3.grady0));
-                hg_st4(t + k, make_float4(e0.t, e1.t, e2.t, e3.t));
+                pb_st4(grad_y + k, make_float4(e0.grady0, e1.grady0, e2.grady0, e3.grady0));
+                pb_st4(t + k, make_float4(e0.t, e1.t, e2.t, e3.t));
             }
-            if (ggx) hg_st4(ggx + k, make_float4(e0.ggx0, e1.ggx0, e2.ggx0, e3.ggx0));
-            if (ggy) hg_st4(ggy + k, make_float4(e0.ggy0, e1.ggy0, e2.ggy0, e3.ggy0));
+            if (ggx) pb_st4(ggx + k, make_float4(e0.ggx0, e1.ggx0, e2.ggx0, e3.ggx0));
+            if (ggy) pb_st4(ggy + k, make_float4(e0.ggy0, e1.ggy0, e2.ggy0, e3.ggy0));
             s += e0.s; s += e1.s; s += e2.s; s += e3.s;
         }
     } else {
@@ -103,26 +97,9 @@ __global__ __launch_bounds__(HG_NT) void halo_grad_pass1(const float *__restrict
         }
     }
     if (!partial) return;                                        // (uniform: no grad0 output, no S)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     __shared__ float red[HG_NT / 64];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float v = 0.f;
-        for (int w = 0; w < HG_NT / 64; ++w) v += red[w];
-        partial[blockIdx.x] = v;
-    }
-}
-
-// one wave per plane folds that plane's per-workgroup partial sums in a fixed order (grad_energy_fold_kernel's form)
-__global__ __launch_bounds__(64) void halo_grad_fold(const float *__restrict__ partial, float *__restrict__ S, int bpp) {
-    const float *p = partial + (long)blockIdx.x * bpp;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < bpp; i += 64) s += p[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (threadIdx.x == 0) S[blockIdx.x] = s;
+    const float v = pb_block_sum_to_first<HG_NT>(s, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = v;
 }
 
 // grad_y -= T;  grad_gx += 2 gx S;  grad_gy += 2 gy S          (nullptr: not asked for)
@@ -139,16 +116,16 @@ __global__ __launch_bounds__(HG_NT) void halo_grad_finish(const float *__restric
         for (long i = 4 * ((long)blk * HG_NT + threadIdx.x); i < HW; i += 4l * bpp * HG_NT) {
             const long k = base + i;
             if (grad_y) {
-                const float4 a = hg_ld4(grad_y + k), b = hg_ld4(T + k);
-                hg_st4(grad_y + k, make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w));
+                const float4 a = pb_ld4(grad_y + k), b = pb_ld4(T + k);
+                pb_st4(grad_y + k, make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w));
             }
             if (ggx) {
-                const float4 a = hg_ld4(ggx + k), b = hg_ld4(gx + k);
-                hg_st4(ggx + k, make_float4(fmaf(b.x, s2, a.x), fmaf(b.y, s2, a.y), fmaf(b.z, s2, a.z), fmaf(b.w, s2, a.w)));
+                const float4 a = pb_ld4(ggx + k), b = pb_ld4(gx + k);
+                pb_st4(ggx + k, make_float4(fmaf(b.x, s2, a.x), fmaf(b.y, s2, a.y), fmaf(b.z, s2, a.z), fmaf(b.w, s2, a.w)));
             }
             if (ggy) {
-                const float4 a = hg_ld4(ggy + k), b = hg_ld4(gy + k);
-                hg_st4(ggy + k, make_float4(fmaf(b.x, s2, a.x), fmaf(b.y, s2, a.y), fmaf(b.z, s2, a.z), fmaf(b.w, s2, a.w)));
+                const float4 a = pb_ld4(ggy + k), b = pb_ld4(gy + k);
+                pb_st4(ggy + k, make_float4(fmaf(b.x, s2, a.x), fmaf(b.y, s2, a.y), fmaf(b.z, s2, a.z), fmaf(b.w, s2, a.w)));
             }
         }
     } else {
@@ -166,12 +143,12 @@ template <bool VEC>
 __global__ __launch_bounds__(HG_NT) void neg_sum_kernel(float *__restrict__ out, const float *__restrict__ other, long n) {
     if constexpr (VEC) {
         for (long i = 4 * ((long)blockIdx.x * HG_NT + threadIdx.x); i < n; i += 4l * gridDim.x * HG_NT) {
-            float4 a = hg_ld4(out + i);
+            float4 a = pb_ld4(out + i);
             if (other) {
-                const float4 b = hg_ld4(other + i);
+                const float4 b = pb_ld4(other + i);
                 a = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
             }
-            hg_st4(out + i, make_float4(-a.x, -a.y, -a.z, -a.w));
+            pb_st4(out + i, make_float4(-a.x, -a.y, -a.z, -a.w));
         }
     } else {
         for (long i = (long)blockIdx.x * HG_NT + threadIdx.x; i < n; i += (long)gridDim.x * HG_NT)
@@ -196,7 +173,7 @@ int pb_fourier_gradients_backward_impl(pb_ctx *ctx, const float *grad_gx, const 
         return pb_fail(ctx, PB_ERR_BADARG, "pb_fourier_gradients_backward: grad_planes may not alias an upstream gradient");
     if (P < 1 || H < 2 || W < 2) return pb_fail(ctx, PB_ERR_BADARG, "bad shape (%d,%d,%d)", P, H, W);
     if ((grad_gx && !pb_fft_length_supported(W)) || (grad_gy && !pb_fft_length_supported(H)))
-        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "planes of %d x %d: lines of up to 65536 samples are supported", H, W);
+        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "planes of %d x %d: lines of up to %d samples are supported", H, W, kMaxLineLength);
     const long n = (long)P * H * W;
     float *other = nullptr;
     if (grad_gx && grad_gy) {
@@ -236,7 +213,7 @@ int pb_halo_mask_backward_impl(pb_ctx *ctx, const float *x, const float *y, cons
     }
     if (B < 1 || C < 1 || H < 2 || W < 2) return pb_fail(ctx, PB_ERR_BADARG, "bad shape (%d,%d,%d,%d)", B, C, H, W);
     if (!pb_fft_length_supported(W))
-        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "image width %d: lines of up to 65536 samples are supported", W);
+        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "image width %d: lines of up to %d samples are supported", W, kMaxLineLength);
     const long HW = (long)H * W;
     const long P = (long)B * C;
     int bpp = (int)((HW + HG_NT * 16 - 1) / (HG_NT * 16));
@@ -276,7 +253,7 @@ int pb_halo_mask_backward_impl(pb_ctx *ctx, const float *x, const float *y, cons
                                grad_y, grad_grad0_x, grad_grad0_y, t, partial, HW, bpp);
         PB_LAUNCH_CHECK();
         if (want_g0) {
-            hipLaunchKernelGGL(halo_grad_fold, dim3((unsigned)P), dim3(64), 0, ctx->stream, partial, S, bpp);
+            hipLaunchKernelGGL(pb_fold_partials_kernel, dim3((unsigned)P), dim3(64), 0, ctx->stream, partial, S, bpp);
             PB_LAUNCH_CHECK();
         }
     }

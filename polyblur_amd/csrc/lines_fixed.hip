@@ -377,8 +377,8 @@ __device__ __forceinline__ void rcentre(cf *s, const float *__restrict__ drev) {
     }
 }
 
-// how a row pair's samples arrive: the image's channels, forming the gray samples exactly as gray_minmax_kernel does
-// (blur_estimation.py:36; estimate.hip:GrayRowsIO) and keeping them for the column pass, with the pair's (min, max) ...
+// how a row pair's samples arrive: the image's channels, forming the gray samples (pb_gray_of, stage_math.h; the loads as
+// estimate.hip:GrayRowsIO) and keeping them for the column pass, with the pair's (min, max) ...
 template <int CC> struct GrayIn {
     const float *row0;         // channel 0, first row of the pair
     long cstride;
@@ -392,8 +392,8 @@ template <int CC> struct GrayIn {
             const float a1 = row0[cstride + p], a2 = row0[2 * cstride + p];
             const float b1 = has1 ? row0[cstride + W + p] : 0.f, b2 = has1 ? row0[2 * cstride + W + p] : 0.f;
             a = a + a1 + a2; b = b + b1 + b2;
-            a = a / 3.0f; b = b / 3.0f;
         }
+        pb_gray_of(a, b, CC, 1.f / (float)CC);
         g0[p] = a;
         lo = fminf(lo, a); hi = fmaxf(hi, a);
         if (has1) { g0[W + p] = b; lo = fminf(lo, b); hi = fmaxf(hi, b); }
@@ -487,11 +487,7 @@ __global__ __launch_bounds__(NTH, rows_waves(R0 * R1 * R2, NTH)) void gray_rows_
     io.lo = INFINITY; io.hi = -INFINITY;
     rows_fixed_body<R0, R1, R2, NTH>(reinterpret_cast<cf *>(sfft), io, gx + (long)b * HW + (long)r0 * W, W, io.has1, tw, drev);
     float lo = io.lo, hi = io.hi;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, o));
-        hi = fmaxf(hi, __shfl_xor(hi, o));
-    }
+    pb_wave_minmax(lo, hi);
     __syncthreads();                                               // (the transform's last reads of sfft)
     float *red = reinterpret_cast<float *>(sfft);
     if ((threadIdx.x & 63) == 0) { red[2 * (threadIdx.x >> 6)] = lo; red[2 * (threadIdx.x >> 6) + 1] = hi; }
@@ -557,11 +553,7 @@ int pb_launch_cols_fixed(pb_ctx *ctx, const float *gray, const float *gx, int P,
     if ((!gy_out && n_angles != 6) || !pl || pl->bluestein_m || pl->nstage != 3 || pl->n != H || lognb < 1 || (W % (2 << lognb)) != 0)
         return PB_ERR_UNSUPPORTED;
     AngleTable7 ang;
-    for (int k = 0; k < 7; ++k) {
-        const float t = n_angles > 0 ? 3.14159265358979323846f * (float)k / (float)n_angles : 0.f;       // (as launch_cols)
-        ang.cs[k] = std::cos(t);
-        ang.sn[k] = std::sin(t);
-    }
+    pb_angle_table(n_angles, ang.cs, ang.sn, 7);
     const int r0 = pl->radix[0], r1 = pl->radix[1], r2 = pl->radix[2];
     const bool sat = discard_sat != 0;
     // The compiled plans: line length = R0 x R1 x R2 in the order launch_cols gives it (smallest radix from 5 up -- or the one whose

@@ -1,4 +1,4 @@
-"""Halo masking on the GPU where the mask can be told from a no-op: halo_kernel, grad_energy_kernel and grad_energy_fold_kernel
+"""Halo masking on the GPU where the mask can be told from a no-op: halo_kernel, grad_energy_kernel and pb_fold_partials_kernel
 (csrc/filters.hip) through pb_halo_mask, the three non-blind C entry points and the Python API, with the caller's gradient
 planes built by tests/halo_ref.py -- sparse and reversed against the output's x-derivative, another energy for every plane, so
 that z = max(M / (nM + M), 0) covers (0, 1) and the mask moves the output by up to 0.7.
