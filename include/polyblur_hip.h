@@ -421,6 +421,14 @@ int pb_dt_normalized_convolution(pb_ctx *ctx, const void *in, void *out, int dty
 /* filters.bilateral_filter (filters.py:107-148), 5x5, sigma_spatial=5, sigma_color=0.1. */
 int pb_bilateral5(pb_ctx *ctx, const void *in, void *out, int dtype, int B, int C, int H, int W);
 
+/* filters.bilateral_filter (filters.py:107-148) with its arguments: per plane, replicate pad of ksize / 2, the weight of a tap
+ * exp(-(dx^2 + dy^2) / (2 sigma_spatial^2)) exp(-(v - centre)^2 / (2 sigma_color^2)), out = sum w v / (sum w + 1e-5).
+ * dtype PB_F32 or PB_F16 (out has the same; fp32 accumulation); in and out (B,C,H,W) DEVICE memory, out may not alias in.
+ * ksize odd, 1 .. PB_KSIZE; both sigma positive and finite -- anything else is PB_ERR_BADARG before any launch.  ksize == 5 is
+ * pb_bilateral5's kernel with these sigma: at 5.0 / 0.1 the same bits.  Asynchronous on the context's stream; no scratch. */
+int pb_bilateral(pb_ctx *ctx, const void *in, void *out, int dtype, int B, int C, int H, int W,
+                 int ksize, float sigma_spatial, float sigma_color);
+
 /* ---- patch decomposition with windowed overlap-add (PolyblurDeblurring(patch_decomposition=True),
  * deblurring.py:269-340; "next" row 1 of SURVEY 8f).  The image is (virtually) replicate-padded by
  * (pad_top, pad_left) to a grid of n_i x n_j patches of ph x pw with strides (step_h, step_w).

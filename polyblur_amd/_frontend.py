@@ -4,7 +4,7 @@ a stream, and the one staging of the three kinds of operand -- a ROCm tensor is 
 tensor and an ``np.ndarray`` go through the GPU, and the result comes back in the kind of ``img``.
 
 torch is not imported here at import time: the package imports without it, and NumPy callers never load it.  The public modules
-(deblurring, nonblind, halo, estimation) import this one and the engine; nothing here imports them back.  The autograd.Functions
+(deblurring, nonblind, halo, estimation, edge_aware) import this one and the engine; nothing here imports them back.  The autograd.Functions
 live in _autograd.py, which the public functions import on first use under grad.
 """
 from __future__ import annotations
@@ -213,7 +213,7 @@ def staged(img, dt, call, extra=(), outputs=_ONE, taps=None, device=None):
     pointers -> (the outputs, in the kind of ``img``; what ``call`` returned).
 
     ``img`` -- a tensor or an array: the caller has checked it -- goes in with NumPy dtype ``dt``; ``extra`` are (pool name,
-    operand) pairs the call reads as float32; each of ``outputs`` is the pool name of an output like ``img`` or a (pool name,
+    operand) pairs the call reads as float32, or (pool name, operand, np.float16) triples it reads as float16; each of ``outputs`` is the pool name of an output like ``img`` or a (pool name,
     shape) pair of float32 words; ``taps``, a (B', kh, kw) host array, becomes the call's KernelSet ``ks``.
 
     A ROCm ``img``: everything stays on its device and on torch's current stream, asynchronously; every temporary is a torch
@@ -231,7 +231,8 @@ def staged(img, dt, call, extra=(), outputs=_ONE, taps=None, device=None):
             outs = [torch.empty_like(xin) if isinstance(o, str) else torch.empty(o[1], dtype=torch.float32, device=img.device) for o in outputs]
             out_ptrs = [o.data_ptr() for o in outs]
         if extra:
-            ex = [torch.as_tensor(e, dtype=torch.float32, device=img.device).contiguous() for _, e in extra]      # (kept alive to the end)
+            ex = [torch.as_tensor(e[1], dtype=torch.float16 if e[2:] == (np.float16,) else torch.float32, device=img.device).contiguous()
+                  for e in extra]                                                                                  # (kept alive to the end)
             extra_ptrs = [e.data_ptr() for e in ex]
         else:
             extra_ptrs = ()
@@ -240,7 +241,7 @@ def staged(img, dt, call, extra=(), outputs=_ONE, taps=None, device=None):
     with bound_engine(None, device) as eng:
         x = np.ascontiguousarray(host_array(img), dtype=dt)
         spec = [(o, x.shape, x.dtype) if isinstance(o, str) else (o[0], o[1], np.float32) for o in outputs]
-        outs, ret = eng.host_call(x, lambda i, o, ex: _invoke(eng, call, taps, i, o, ex), [(name, host_array(e)) for name, e in extra], spec)
+        outs, ret = eng.host_call(x, lambda i, o, ex: _invoke(eng, call, taps, i, o, ex), [(e[0], host_array(e[1])) + tuple(e[2:]) for e in extra], spec)
     if not array:
         import torch
         outs = [torch.from_numpy(o) for o in outs]

@@ -6,6 +6,8 @@
 #include "stage_math.h"
 
 int pb_fourier_gradients_impl(pb_ctx *ctx, const float *planes, int P, int H, int W, float *gx, float *gy);
+int pb_bilateral5_sigma_impl(pb_ctx *ctx, const void *in, int in_dtype, void *out, int out_dtype, int P, int H, int W,
+                             double sigma_space, double sigma_color);
 
 namespace {
 
@@ -1189,7 +1191,13 @@ int pb_recombine(pb_ctx *ctx, const float *y, const void *cur, int cur_dtype, co
 }
 
 int pb_bilateral5_impl(pb_ctx *ctx, const void *in, int in_dtype, void *out, int out_dtype, int P, int H, int W) {
-    const double sigma_color = 0.1, sigma_space = 5.0, log2e = 1.4426950408889634;
+    return pb_bilateral5_sigma_impl(ctx, in, in_dtype, out, out_dtype, P, H, W, 5.0, 0.1);
+}
+
+// the same launch with the caller's two sigma (pb_bilateral at ksize == 5, bilateral.hip); 5.0f and 0.1f give the floats 5.0 and 0.1 give
+int pb_bilateral5_sigma_impl(pb_ctx *ctx, const void *in, int in_dtype, void *out, int out_dtype, int P, int H, int W,
+                             double sigma_space, double sigma_color) {
+    const double log2e = 1.4426950408889634;
     const float ivc = (float)(-log2e / (2. * sigma_color * sigma_color)), ivs = (float)(-log2e / (2. * sigma_space * sigma_space));   // (exp2's arguments)
     dim3 grid((W + 63) / 64, (H + 15) / 16, P < 65535 ? P : 65535);
     ProfScope prof(ctx, PB_PROF_PREFILTER);

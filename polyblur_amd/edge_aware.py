@@ -1,0 +1,119 @@
+"""The edge-aware smoothing behind ``prefiltering=True`` as public functions (reference filters.py:107-148,
+domain_transform.py:6-85, deblurring.py:99-110):
+
+    from polyblur_amd import bilateral_filter, recursive_filter, normalized_convolution, edge_aware_filtering
+
+``bilateral_filter(I, ksize=5, sigma_spatial=5.0, sigma_color=0.1)``, ``recursive_filter(I, sigma_s=60, sigma_r=0.4,
+num_iterations=3, joint_image=None)`` and ``normalized_convolution(I, sigma_s=60, sigma_r=0.4, num_iterations=3)`` have the
+reference's names, arguments and defaults; ``edge_aware_filtering(img, sigma_s, sigma_r, *, prefilter='bilateral')`` ->
+``(img_smoothed, img_noise)`` with the three values of ``prefilter`` that ``polyblur_deblurring`` takes.  ``I`` is a (B,C,H,W)
+float32 or float16 ``torch.Tensor`` -- on a ROCm device (used in place, on torch's current stream) or on the CPU (staged through
+the GPU) -- or ``np.ndarray``; the result has the kind, device and dtype of ``I``.
+
+The bilateral window is any odd ``ksize`` from 1 to 25 (an even one is refused: the reference puts an even window's spatial
+weights one sample off its taps, filters.py:109 against utils.pad_with_kernel).  Forward only: with autograd on, an operand that
+requires grad is refused before any device work; under ``torch.no_grad()`` the call runs.
+
+The filters are the HIP engine's (pb_bilateral, pb_dt_recursive_filter, pb_dt_normalized_convolution); ``img_noise`` is the
+subtraction ``img - img_smoothed`` in the image's own kind, as the reference writes it.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from . import _capi as capi
+from ._frontend import _PREFILTER, DTYPES, check_image, refuse_under_grad, staged, wants_grad
+
+_NO_GRAD = "the edge-aware filters are not differentiated"
+_NC_MAX_SIDE = 8190                                # pb_dt_normalized_convolution: H, W <= 8190
+_SIGMA_MIN = 1e-18                                 # below it -1 / (2 sigma^2) is not a float32
+
+
+def _positive(name, v, least=0.0):
+    v = float(v)
+    if not (v > 0 and math.isfinite(v)):
+        raise ValueError("%s must be positive and finite, got %r" % (name, v))
+    if v < least:
+        raise ValueError("%s must be at least %g, got %r" % (name, least, v))
+    return v
+
+
+def _iterations(n):
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+        raise TypeError("num_iterations must be an integer, got %r" % (n,))
+    if n < 1:
+        raise ValueError("num_iterations must be at least 1, got %d" % n)
+    return int(n)
+
+
+def bilateral_filter(I, ksize=5, sigma_spatial=5.0, sigma_color=0.1):
+    """filters.bilateral_filter (filters.py:107-148): per plane, replicate pad of ``ksize // 2``, the weight of a tap
+    exp(-(dx^2 + dy^2) / (2 sigma_spatial^2)) exp(-(v - centre)^2 / (2 sigma_color^2)), sum w v / (sum w + 1e-5)."""
+    shape, dt = check_image(I, allow_half=True)
+    if isinstance(ksize, bool) or not isinstance(ksize, (int, np.integer)):
+        raise TypeError("ksize must be an integer, got %r" % (ksize,))
+    if ksize % 2 == 0:
+        raise NotImplementedError("an even ksize is not built: the reference's even window puts its spatial weights one sample "
+                                  "off its taps (got %d)" % ksize)
+    if not 1 <= ksize <= capi.PB_KSIZE:
+        raise NotImplementedError("ksize must be odd, from 1 to %d (got %d)" % (capi.PB_KSIZE, ksize))
+    ss, sc = _positive("sigma_spatial", sigma_spatial, _SIGMA_MIN), _positive("sigma_color", sigma_color, _SIGMA_MIN)
+    if wants_grad(I):
+        refuse_under_grad("bilateral_filter", _NO_GRAD)
+    return staged(I, dt, lambda eng, i, o, ex: eng.bilateral_ptr(i, o[0], DTYPES[dt], shape, int(ksize), ss, sc))[0][0]
+
+
+def recursive_filter(I, sigma_s=60, sigma_r=0.4, num_iterations=3, joint_image=None):
+    """domain_transform.recursive_filter (domain_transform.py:6-85): the domain-transform recursive filter, guided by
+    ``joint_image`` (an image of ``I``'s shape, read in ``I``'s dtype) or by ``I`` itself."""
+    shape, dt = check_image(I, allow_half=True)
+    ss, sr, n = _positive("sigma_s", sigma_s), _positive("sigma_r", sigma_r), _iterations(num_iterations)
+    extra = ()
+    if joint_image is not None:
+        try:
+            jshape, _ = check_image(joint_image, allow_half=True)
+        except TypeError as e:
+            raise TypeError("joint_image: %s" % e) from None
+        except ValueError:
+            jshape = None
+        if jshape != shape:
+            raise ValueError("joint_image must have the image's shape %r, got %r" % (shape, tuple(joint_image.shape)))
+        extra = (("np.joint", joint_image, dt.type),)
+    if wants_grad(I, joint_image):
+        refuse_under_grad("recursive_filter", _NO_GRAD)
+    return staged(I, dt, lambda eng, i, o, ex: eng.dt_recursive_filter_ptr(i, ex[0] if ex else None, o[0], DTYPES[dt], shape, ss, sr, n),
+                  extra)[0][0]
+
+
+def normalized_convolution(I, sigma_s=60, sigma_r=0.4, num_iterations=3):
+    """The domain transform's normalized convolution (NC.cpp:143-204), per image; H and W up to 8190."""
+    shape, dt = check_image(I, allow_half=True)
+    ss, sr, n = _positive("sigma_s", sigma_s), _positive("sigma_r", sigma_r), _iterations(num_iterations)
+    if shape[2] > _NC_MAX_SIDE or shape[3] > _NC_MAX_SIDE:
+        raise NotImplementedError("normalized_convolution is built for H and W up to %d, got %d x %d" % (_NC_MAX_SIDE, shape[2], shape[3]))
+    if wants_grad(I):
+        refuse_under_grad("normalized_convolution", _NO_GRAD)
+    return staged(I, dt, lambda eng, i, o, ex: eng.dt_normalized_convolution_ptr(i, o[0], DTYPES[dt], shape, ss, sr, n))[0][0]
+
+
+def edge_aware_filtering(img, sigma_s, sigma_r, *, prefilter='bilateral'):
+    """deblurring.edge_aware_filtering (deblurring.py:99-110) -> (img_smoothed, img_noise = img - img_smoothed).
+    ``prefilter``: 'bilateral' -- the reference's live path, ``bilateral_filter(img)`` with its defaults, ``sigma_s`` and
+    ``sigma_r`` unused (:107-108) --, 'domain_transform' (``recursive_filter`` with one iteration) or 'normalized_convolution'
+    (``normalized_convolution`` with one iteration)."""
+    check_image(img, allow_half=True)
+    if prefilter not in _PREFILTER:
+        raise ValueError("prefilter must be 'bilateral', 'domain_transform' or 'normalized_convolution'")
+    if wants_grad(img):
+        refuse_under_grad("edge_aware_filtering", _NO_GRAD)
+    if prefilter == "bilateral":
+        smooth = bilateral_filter(img)
+    elif prefilter == "domain_transform":
+        smooth = recursive_filter(img, sigma_s=sigma_s, sigma_r=sigma_r, num_iterations=1)
+    else:
+        smooth = normalized_convolution(img, sigma_s=sigma_s, sigma_r=sigma_r, num_iterations=1)
+    if isinstance(img, np.ndarray):
+        return smooth, (img.astype(smooth.dtype, copy=False) - smooth)
+    return smooth, img.detach() - smooth

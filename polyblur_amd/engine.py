@@ -179,13 +179,13 @@ class Engine:
     # ---- numpy conveniences (host arrays in, host arrays out) -------------------------------
     def host_call(self, x: np.ndarray, call, extra=(), outputs=None, sync=True):
         """The one upload / call / download of host data: x goes to "np.in", each (pool name, array) of `extra` to its buffer as
-        float32; call(in_ptr, out_ptrs, extra_ptrs) runs on the context's stream; `outputs` -- (pool name, shape, dtype) each,
+        float32 (a third element: as that dtype); call(in_ptr, out_ptrs, extra_ptrs) runs on the context's stream; `outputs` -- (pool name, shape, dtype) each,
         by default one like x in "np.out" -- come back as arrays.  -> (outputs, what call returned).  `sync`: wait for the
         stream before the download (which waits for it as well: whether a method says so is kept as it was written)."""
         din = self.to_device("np.in", x)
         spec = [("np.out", x.shape, x.dtype)] if outputs is None else outputs
         bufs = [self.buffer(name, int(np.prod(shape)) * np.dtype(dt).itemsize) for name, shape, dt in spec]
-        ex = [self.to_device(name, np.ascontiguousarray(a, np.float32)).ptr for name, a in extra]
+        ex = [self.to_device(name, np.ascontiguousarray(a, dt[0] if dt else np.float32)).ptr for name, a, *dt in extra]
         ret = call(din.ptr, [b.ptr for b in bufs], ex)
         if sync:
             self.synchronize()
@@ -413,6 +413,25 @@ class Engine:
         x = np.ascontiguousarray(x)
         B, Cc, H, W = x.shape
         return self._one(x, lambda i, o: self._check(self.lib.pb_bilateral5(self.ctx, i, o, _DT[x.dtype], B, Cc, H, W)))
+
+    # ---- the edge-aware filters on device pointers (polyblur_amd/edge_aware.py) ------------------------------------------
+    def bilateral_ptr(self, in_ptr: int, out_ptr: int, dtype: int, shape, ksize, sigma_spatial, sigma_color):
+        """the bilateral filter with an odd window of up to 25 x 25 (pb_bilateral; 5: pb_bilateral5's kernel); asynchronous"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_bilateral(self.ctx, in_ptr, out_ptr, int(dtype), B, Cc, H, W, int(ksize), float(sigma_spatial),
+                                          float(sigma_color)))
+
+    def dt_recursive_filter_ptr(self, in_ptr: int, joint_ptr, out_ptr: int, dtype: int, shape, sigma_s, sigma_r, num_iterations):
+        """joint_ptr: an image like the input's, of its dtype, or None for the input itself (pb_dt_recursive_filter); asynchronous"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_dt_recursive_filter(self.ctx, in_ptr, joint_ptr, out_ptr, int(dtype), B, Cc, H, W, float(sigma_s),
+                                                    float(sigma_r), int(num_iterations)))
+
+    def dt_normalized_convolution_ptr(self, in_ptr: int, out_ptr: int, dtype: int, shape, sigma_s, sigma_r, num_iterations):
+        """pb_dt_normalized_convolution (H, W <= 8190); asynchronous"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_dt_normalized_convolution(self.ctx, in_ptr, out_ptr, int(dtype), B, Cc, H, W, float(sigma_s),
+                                                          float(sigma_r), int(num_iterations)))
 
     # ---- the patch lattice of PolyblurDeblurring(patch_decomposition=True) on device pointers -----------------------------
     def extract_patches_ptr(self, in_ptr: int, patches_ptr: int, dtype: int, shape, grid: dict, first: int, count: int):
