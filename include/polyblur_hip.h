@@ -429,6 +429,17 @@ int pb_bilateral5(pb_ctx *ctx, const void *in, void *out, int dtype, int B, int 
 int pb_bilateral(pb_ctx *ctx, const void *in, void *out, int dtype, int B, int C, int H, int W,
                  int ksize, float sigma_spatial, float sigma_color);
 
+/* pb_bilateral_backward: the backward of pb_bilateral with respect to the image (prefiltering=True under autograd; no gradient
+ * with respect to the two sigma).  in, grad_out (the upstream gradient of out) and grad_in are (B,C,H,W) float32 DEVICE memory;
+ * grad_in is written, not accumulated, and may alias neither input.  Shapes, window sizes and sigma as pb_bilateral's (odd ksize
+ * from 1 to PB_KSIZE, 5 included); anything else is PB_ERR_BADARG before any launch.  D and out are formed again by the backward's
+ * own arithmetic -- the filter has no kink, so nothing depends on the forward's bits.  Three launches: the centre term with out
+ * and G = grad_out / (D + 1e-5), the tap term gathered over the replicate-padded domain, the fold of the pad.  Scratch: two plane
+ * sets ("bilg.out", "bilg.G") and one padded plane set of (H + ksize - 1) x (W + ksize - 1) ("bilg.T").  fp32 sums in an order
+ * the shape alone fixes, no float atomics: the same call gives the same bits.  Asynchronous on the context's stream.          */
+int pb_bilateral_backward(pb_ctx *ctx, const float *in, const float *grad_out, float *grad_in, int B, int C, int H, int W,
+                          int ksize, float sigma_spatial, float sigma_color);
+
 /* ---- patch decomposition with windowed overlap-add (PolyblurDeblurring(patch_decomposition=True),
  * deblurring.py:269-340; "next" row 1 of SURVEY 8f).  The image is (virtually) replicate-padded by
  * (pad_top, pad_left) to a grid of n_i x n_j patches of ph x pw with strides (step_h, step_w).

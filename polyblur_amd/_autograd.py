@@ -1,4 +1,4 @@
-"""The package's autograd.Functions (DESIGN.md 4.7-4.9): the forward and backward passes are the engine's, on ROCm float32
+"""The package's autograd.Functions (DESIGN.md 4.7-4.9, 4.12): the forward and backward passes are the engine's, on ROCm float32
 tensors and torch's current stream; no double backward.  The public functions import this module on first use under grad --
 it is the only one that needs torch at import time -- after every check and refusal of theirs has passed."""
 from __future__ import annotations
@@ -149,3 +149,26 @@ class HaloMaskingFunction(torch.autograd.Function):
             eng.halo_mask_backward_ptr(x.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), g.data_ptr(),
                                        *[o.data_ptr() if o is not None else None for o in outs], x.shape)
         return tuple(outs) + (None,)
+
+
+class BilateralFunction(torch.autograd.Function):
+    """bilateral_filter of a ROCm float32 tensor, differentiated with respect to the image (the two sigma are Python floats).
+    filt: image -> the filtered image (edge_aware._bilateral)"""
+
+    @staticmethod
+    def forward(ctx, img, ksize, sigma_spatial, sigma_color, filt):
+        x = img.detach().contiguous()
+        out = filt(x, ksize, sigma_spatial, sigma_color)
+        ctx.save_for_backward(x)
+        ctx.pb = (int(ksize), float(sigma_spatial), float(sigma_color))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        (x,) = ctx.saved_tensors
+        g = _upstream(grad_out)
+        gin = torch.empty_like(x)
+        with bound_engine(x) as eng:
+            eng.bilateral_backward_ptr(x.data_ptr(), g.data_ptr(), gin.data_ptr(), x.shape, *ctx.pb)
+        return gin, None, None, None, None

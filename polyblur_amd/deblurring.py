@@ -23,6 +23,10 @@ behaviour): ``support`` ('full' | 'adaptive'), ``prefilter`` ('bilateral' |
 'domain_transform' -- which edge-aware filter ``prefiltering=True`` uses; the reference's
 live code path is the bilateral one, deblurring.py:107-108), ``return_info``, ``temporaries``
 ('fp32' | 'fp16': float16 tensors only -- store the two Horner temporaries as fp16).
+
+A float32 ROCm tensor that requires grad takes the differentiable composition (``_blind_under_grad``): estimation, non-blind
+step, ``remove_halo=True`` and ``prefiltering=True`` with the bilateral prefilter have the engine's own backward passes;
+``edgetaping``, the other two prefilters, ``q > 0`` and the patch decomposition are refused before any device work.
 """
 from __future__ import annotations
 
@@ -31,8 +35,9 @@ from time import time
 import numpy as np
 
 from . import _capi as capi
-from ._frontend import (CPU_WITH_GRAD, DTYPES, FLOAT32_ONLY, HALO_ONLY, NO_EDGETAPER, NO_QUANTILE, bound_engine, build_options,
-                        check_image_size, is_tensor, refuse_under_grad, staged, wants_grad)
+from ._frontend import (_PREFILTER, CPU_WITH_GRAD, DTYPES, FLOAT32_ONLY, HALO_ONLY, NO_EDGETAPER, NO_QUANTILE, bound_engine,
+                        build_options, check_image_size, is_tensor, refuse_under_grad, staged, wants_grad)
+from .edge_aware import edge_aware_filtering
 from .estimation import gaussian_blur_estimation
 from .halo import fourier_gradients
 from .nonblind import inverse_filtering_rank3
@@ -107,7 +112,8 @@ def polyblur_deblurring(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, sigma_
             raise TypeError("tensor dtype must be float32 or float16 (the reference is float32-only)")
         if wants_grad(img):
             return _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_interpolated_angles, remove_halo, edgetaping,
-                                     prefiltering, discard_saturation, multichannel_kernel, method, support, return_info, temporaries)
+                                     prefiltering, discard_saturation, multichannel_kernel, method, support, return_info, temporaries,
+                                     prefilter, sigma_s, sigma_r)
         x, dt = img, (np.float32 if img.dtype == torch.float32 else np.float16)
     check_image_size(*x.shape[-2:])
     if temporaries == "fp16" and dt != np.float16:
@@ -127,19 +133,25 @@ def polyblur_deblurring(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, sigma_
 
 
 def _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_interpolated_angles, remove_halo, edgetaping,
-                      prefiltering, discard_saturation, multichannel_kernel, method, support, return_info, temporaries):
+                      prefiltering, discard_saturation, multichannel_kernel, method, support, return_info, temporaries, prefilter,
+                      sigma_s, sigma_r):
     """polyblur_deblurring of a tensor that requires grad (the reference's README: "fully differentiable"): the blind call as a
-    composition of the package's own differentiable functions -- estimate (estimation.py), non-blind step
-    (nonblind.py; 4.7) with the halo mask where asked (halo.py; 4.9), clip, n_iter times (deblurring.py:54-90).  Every refusal
-    comes before any device work."""
+    composition of the package's own differentiable functions -- estimate (estimation.py), with ``prefiltering``
+    the bilateral split (edge_aware.py; 4.12: the step runs on the smooth part and the noise is added back, deblurring.py:80-84),
+    non-blind step (nonblind.py; 4.7) with the halo mask where asked (halo.py; 4.9), clip, n_iter times (deblurring.py:54-90).
+    Every refusal comes before any device work."""
     import torch
     what = "polyblur_deblurring"
     if remove_halo and not (img.is_cuda and img.dtype == torch.float32):     # (the stage's device check first: its reason names the stage)
         refuse_under_grad(what + "(remove_halo=True)", HALO_ONLY)
-    for flag, name, why in ((edgetaping, "edgetaping", NO_EDGETAPER),
-                            (prefiltering, "prefiltering", "the edge-aware prefilters are not differentiated")):
-        if flag:
-            refuse_under_grad("%s(%s=True)" % (what, name), why)
+    if edgetaping:
+        refuse_under_grad(what + "(edgetaping=True)", NO_EDGETAPER)
+    if prefiltering:
+        rocm_float32 = img.is_cuda and img.dtype == torch.float32
+        if rocm_float32 and prefilter not in _PREFILTER:
+            raise ValueError("prefilter must be 'bilateral', 'domain_transform' or 'normalized_convolution'")     # (build_options')
+        if not (rocm_float32 and prefilter == "bilateral"):                  # (the bilateral filter's backward alone is built: 4.12)
+            refuse_under_grad(what + "(prefiltering=True)", "the edge-aware prefilters are not differentiated")
     if q > 0:
         refuse_under_grad("%s(q=%g)" % (what, q), NO_QUANTILE)
     if method == "direct_separable":
@@ -166,7 +178,12 @@ def _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_i
     for _ in range(int(n_iter)):
         kernel = gaussian_blur_estimation(x, q=0, n_angles=n_angles, n_interpolated_angles=n_interpolated_angles, c=c, b=b,
                                           ker_size=ker_size, discard_saturation=discard_saturation, multichannel=multichannel_kernel)
-        x = inverse_filtering_rank3(x, kernel, alpha, beta, remove_halo=bool(remove_halo), grad_img=grad_img, method=method).clip(0, 1)
+        if prefiltering:                                                     # (deblurring.py:80-84; the mask's x is the smooth part)
+            smooth, noise = edge_aware_filtering(x, sigma_s, sigma_r, prefilter=prefilter)
+            x = (inverse_filtering_rank3(smooth, kernel, alpha, beta, remove_halo=bool(remove_halo), grad_img=grad_img, method=method)
+                 + noise).clip(0, 1)
+        else:
+            x = inverse_filtering_rank3(x, kernel, alpha, beta, remove_halo=bool(remove_halo), grad_img=grad_img, method=method).clip(0, 1)
     return x if n_iter > 0 else img.clone()
 
 

@@ -11,8 +11,14 @@ float32 or float16 ``torch.Tensor`` -- on a ROCm device (used in place, on torch
 the GPU) -- or ``np.ndarray``; the result has the kind, device and dtype of ``I``.
 
 The bilateral window is any odd ``ksize`` from 1 to 25 (an even one is refused: the reference puts an even window's spatial
-weights one sample off its taps, filters.py:109 against utils.pad_with_kernel).  Forward only: with autograd on, an operand that
-requires grad is refused before any device work; under ``torch.no_grad()`` the call runs.
+weights one sample off its taps, filters.py:109 against utils.pad_with_kernel).
+
+Gradients: with autograd on and ``I`` a float32 ROCm tensor that requires grad, ``bilateral_filter`` returns a
+tensor with a ``grad_fn`` -- the same bits as under ``torch.no_grad()``; the backward pass is the engine's
+(pb_bilateral_backward), with respect to the image, no double backward -- and ``edge_aware_filtering(prefilter='bilateral')``
+returns ``(img_smoothed, img - img_smoothed)``, both in the graph.  Every other operand that requires grad -- a CPU or float16
+tensor, ``recursive_filter``, ``normalized_convolution``, the other two values of ``prefilter``, a ``joint_image`` -- is refused
+before any device work; under ``torch.no_grad()`` the call runs.
 
 The filters are the HIP engine's (pb_bilateral, pb_dt_recursive_filter, pb_dt_normalized_convolution); ``img_noise`` is the
 subtraction ``img - img_smoothed`` in the image's own kind, as the reference writes it.
@@ -24,7 +30,7 @@ import math
 import numpy as np
 
 from . import _capi as capi
-from ._frontend import _PREFILTER, DTYPES, check_image, refuse_under_grad, staged, wants_grad
+from ._frontend import _PREFILTER, DTYPES, check_image, is_rocm_float32, refuse_under_grad, staged, wants_grad
 
 _NO_GRAD = "the edge-aware filters are not differentiated"
 _NC_MAX_SIDE = 8190                                # pb_dt_normalized_convolution: H, W <= 8190
@@ -48,10 +54,17 @@ def _iterations(n):
     return int(n)
 
 
+def _bilateral(I, ksize, ss, sc, dt=np.dtype(np.float32)):
+    """the one call of pb_bilateral: the public function's forward, and BilateralFunction's"""
+    shape = tuple(I.shape)
+    return staged(I, dt, lambda eng, i, o, ex: eng.bilateral_ptr(i, o[0], DTYPES[dt], shape, int(ksize), ss, sc))[0][0]
+
+
 def bilateral_filter(I, ksize=5, sigma_spatial=5.0, sigma_color=0.1):
     """filters.bilateral_filter (filters.py:107-148): per plane, replicate pad of ``ksize // 2``, the weight of a tap
-    exp(-(dx^2 + dy^2) / (2 sigma_spatial^2)) exp(-(v - centre)^2 / (2 sigma_color^2)), sum w v / (sum w + 1e-5)."""
-    shape, dt = check_image(I, allow_half=True)
+    exp(-(dx^2 + dy^2) / (2 sigma_spatial^2)) exp(-(v - centre)^2 / (2 sigma_color^2)), sum w v / (sum w + 1e-5).
+    Differentiable with respect to ``I`` when it is a float32 ROCm tensor that requires grad (the module docstring)."""
+    _, dt = check_image(I, allow_half=True)
     if isinstance(ksize, bool) or not isinstance(ksize, (int, np.integer)):
         raise TypeError("ksize must be an integer, got %r" % (ksize,))
     if ksize % 2 == 0:
@@ -61,8 +74,11 @@ def bilateral_filter(I, ksize=5, sigma_spatial=5.0, sigma_color=0.1):
         raise NotImplementedError("ksize must be odd, from 1 to %d (got %d)" % (capi.PB_KSIZE, ksize))
     ss, sc = _positive("sigma_spatial", sigma_spatial, _SIGMA_MIN), _positive("sigma_color", sigma_color, _SIGMA_MIN)
     if wants_grad(I):
-        refuse_under_grad("bilateral_filter", _NO_GRAD)
-    return staged(I, dt, lambda eng, i, o, ex: eng.bilateral_ptr(i, o[0], DTYPES[dt], shape, int(ksize), ss, sc))[0][0]
+        if not is_rocm_float32(I):
+            refuse_under_grad("bilateral_filter", _NO_GRAD)
+        from ._autograd import BilateralFunction
+        return BilateralFunction.apply(I, int(ksize), ss, sc, _bilateral)
+    return _bilateral(I, int(ksize), ss, sc, dt)
 
 
 def recursive_filter(I, sigma_s=60, sigma_r=0.4, num_iterations=3, joint_image=None):
@@ -102,11 +118,13 @@ def edge_aware_filtering(img, sigma_s, sigma_r, *, prefilter='bilateral'):
     """deblurring.edge_aware_filtering (deblurring.py:99-110) -> (img_smoothed, img_noise = img - img_smoothed).
     ``prefilter``: 'bilateral' -- the reference's live path, ``bilateral_filter(img)`` with its defaults, ``sigma_s`` and
     ``sigma_r`` unused (:107-108) --, 'domain_transform' (``recursive_filter`` with one iteration) or 'normalized_convolution'
-    (``normalized_convolution`` with one iteration)."""
+    (``normalized_convolution`` with one iteration).  Under grad (a float32 ROCm ``img`` that requires grad, 'bilateral'): both
+    results are in the graph."""
     check_image(img, allow_half=True)
     if prefilter not in _PREFILTER:
         raise ValueError("prefilter must be 'bilateral', 'domain_transform' or 'normalized_convolution'")
-    if wants_grad(img):
+    under_grad = wants_grad(img)
+    if under_grad and not (prefilter == "bilateral" and is_rocm_float32(img)):
         refuse_under_grad("edge_aware_filtering", _NO_GRAD)
     if prefilter == "bilateral":
         smooth = bilateral_filter(img)
@@ -116,4 +134,4 @@ def edge_aware_filtering(img, sigma_s, sigma_r, *, prefilter='bilateral'):
         smooth = normalized_convolution(img, sigma_s=sigma_s, sigma_r=sigma_r, num_iterations=1)
     if isinstance(img, np.ndarray):
         return smooth, (img.astype(smooth.dtype, copy=False) - smooth)
-    return smooth, img.detach() - smooth
+    return smooth, (img if under_grad else img.detach()) - smooth

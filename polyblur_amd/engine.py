@@ -421,6 +421,12 @@ class Engine:
         self._check(self.lib.pb_bilateral(self.ctx, in_ptr, out_ptr, int(dtype), B, Cc, H, W, int(ksize), float(sigma_spatial),
                                           float(sigma_color)))
 
+    def bilateral_backward_ptr(self, in_ptr: int, grad_out_ptr: int, grad_in_ptr: int, shape, ksize, sigma_spatial, sigma_color):
+        """d loss / d image of bilateral_ptr's filter, float32 (pb_bilateral_backward); grad_in may alias neither input; asynchronous"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_bilateral_backward(self.ctx, in_ptr, grad_out_ptr, grad_in_ptr, B, Cc, H, W, int(ksize),
+                                                   float(sigma_spatial), float(sigma_color)))
+
     def dt_recursive_filter_ptr(self, in_ptr: int, joint_ptr, out_ptr: int, dtype: int, shape, sigma_s, sigma_r, num_iterations):
         """joint_ptr: an image like the input's, of its dtype, or None for the input itself (pb_dt_recursive_filter); asynchronous"""
         B, Cc, H, W = (int(v) for v in shape)
