@@ -278,11 +278,6 @@ struct Geometry {
     // ker_size above 25: the taps on the ker_size grid (conv_big.hip), rebuilt after every estimation; a caller's kernel set
     // beyond the 25 x 25 record (pb_taps): its table for the call's boundary
     BigTaps big;
-    // the records are point-symmetric Gaussians the estimation of THIS call builds on an odd ker_size grid (PolySpec.always)
-    bool est_gaussians = false;
-    // ... and every one of them takes the window form of a single pass (PolySpec.always == 2): the edgetaper's three blends
-    // issue the wave body's launch and nothing else
-    bool taper_windows = false;
     // the polynomial is the one with the pure-phase filter (conv_phase.hip): the caller's raw kh x kw taps, one kernel per image
     const float *phase_taps = nullptr;
     int phase_kh = 0, phase_kw = 0;
@@ -323,10 +318,29 @@ void set_out_interior(ConvPass &p, const Geometry &g, void *ptr, int dtype) {
     p.out = ptr; p.out_kind = OUT_INTERIOR; p.out_dtype = dtype; p.out_pitch = g.W; p.out_plane = g.HW;
 }
 
+// the kernels' own spectra, every kernel on the window form of a single pass (PolySpec.always == 2)
+PolySpec window_form_spec() {
+    PolySpec ps = no_poly();
+    ps.always = 2;
+    return ps;
+}
+
+// What one iteration of the pipeline asks of the spectra it builds and meets: worked out ONCE, in front of the estimation
+// (pb_polyblur_batch), and handed to the estimation, the edgetaper's blends and the polynomial alike -- the estimation ends with
+// exactly the spectra the passes behind it ask for.  A stage entry point has no plan: its blends are plain passes, its
+// polynomial works its spec out itself (poly_spec), and every selection goes to slot 0.
+struct IterPlan {
+    int slot = 0;                                    // this iteration's slot of the selection scratch (pb_body_selection)
+    PolySpec blends = no_poly();                     // the edgetaper's three blends
+    PolySpec poly = no_poly();                       // the polynomial
+    PolySpec est1 = no_poly(), est2 = no_poly();     // what the estimation builds into the first / the second set (est2 all zero: no second set)
+};
+
 // Three edgetaper blends on the padded domain (edgetaper.py:26-33).  src is an un-padded image
 // (virtual replicate pad).  Returns the padded fp32 result in *result (one of the two scratch planes).
+// want.spec: no_poly(), or window_form_spec() where the estimation built these records' spectra under it (one launch per blend)
 int run_edgetaper(pb_ctx *ctx, const Geometry &g, const void *src, int src_dtype, const pb_blur_info *info, int boundary,
-                  float *pa, float *pb, float **result) {
+                  float *pa, float *pb, float **result, const PassWant &want) {
     ConvPass p = base_pass(g, info, boundary);
     p.epilogue = EPI_TAPER;
     set_in_virtual(p, g, src, src_dtype);
@@ -344,36 +358,34 @@ int run_edgetaper(pb_ctx *ctx, const Geometry &g, const void *src, int src_dtype
         *result = pa;
         return rcb;
     }
-    // (the spec the estimation built these records' spectra under: every kernel on the window form, one launch per blend)
-    struct SpecScope { pb_ctx *c; ~SpecScope() { c->poly_want = no_poly(); } } scope{ctx};
-    if (g.taper_windows) { ctx->poly_want = no_poly(); ctx->poly_want.always = 2; }
-    int rc = pb_launch_conv(ctx, p);
+    int rc = pb_launch_conv(ctx, p, want);
     if (rc) return rc;
     // (window form for every image: the second and the third blend only touch the ring of window pairs on which alpha < 1
     // can reach them -- the rest of `pa` keeps the first blend's copy of the image, which is what three blends with alpha = 1
     // leave there; `pb` is only ever read inside the second blend's ring)
-    const int ring2 = g.taper_windows && ctx->taper_ring ? 5 : 0, ring3 = g.taper_windows && ctx->taper_ring ? 4 : 0;
+    const bool rings = want.spec.always == 2 && ctx->taper_ring;
     set_in_padded(p, g, pa); set_x_padded(p, g, pa); set_out_padded(p, g, pb);
-    p.ring = ring2;
-    rc = pb_launch_conv(ctx, p);
+    p.ring = rings ? 5 : 0;
+    rc = pb_launch_conv(ctx, p, want);
     if (rc) return rc;
     set_in_padded(p, g, pb); set_x_padded(p, g, pb); set_out_padded(p, g, pa);
-    p.ring = ring3;
-    rc = pb_launch_conv(ctx, p);
+    p.ring = rings ? 4 : 0;
+    rc = pb_launch_conv(ctx, p, want);
     *result = pa;
     return rc;
 }
 
 // The three Horner steps of y = a3 K^3 x + a2 K^2 x + a1 K x + beta x (deblurring.py:122-138).
-void make_steps(const Geometry &g, const void *xsrc, int x_dtype, const float *xpadded, const pb_blur_info *info, float alpha,
+// x: the un-padded image of x_dtype (virtual pad), or -- x_padded -- a padded fp32 plane (after an edgetaper)
+void make_steps(const Geometry &g, const void *x, int x_dtype, bool x_padded, const pb_blur_info *info, float alpha,
                 float beta, int boundary, float *t1, float *t2, void *dst, int dst_dtype, int clamp01, ConvPass *steps) {
     const float a3 = alpha / 2 - beta + 2, a2 = 3 * beta - alpha - 6, a1 = 5 - 3 * beta + alpha / 2;
     ConvPass p = base_pass(g, info, boundary);
-    auto set_x = [&](ConvPass &q) { if (xpadded) set_x_padded(q, g, xpadded); else set_x_virtual(q, g, xsrc, x_dtype); };
+    auto set_x = [&](ConvPass &q) { if (x_padded) set_x_padded(q, g, static_cast<const float *>(x)); else set_x_virtual(q, g, x, x_dtype); };
     const int tdt = g.t1h ? PB_F16 : PB_F32;
     void *T1 = g.t1h ? g.t1h : static_cast<void *>(t1), *T2 = g.t2h ? g.t2h : static_cast<void *>(t2);
     // t1 = K * (a3 x) + a2 x
-    if (xpadded) set_in_padded(p, g, xpadded); else set_in_virtual(p, g, xsrc, x_dtype);
+    if (x_padded) set_in_padded(p, g, x); else set_in_virtual(p, g, x, x_dtype);
     set_x(p); set_out_padded(p, g, T1, tdt);
     p.scale = a3; p.coef = a2;
     steps[0] = p;
@@ -387,18 +399,20 @@ void make_steps(const Geometry &g, const void *xsrc, int x_dtype, const float *x
     steps[2] = p;
 }
 
-// what the spectra of a polynomial with these steps should be those of (PolySpec; conv.hip: pb_poly_spec_mode)
+// What the spectra of a polynomial should be those of (PolySpec; conv.hip: pb_poly_spec_mode).  A function of the context's
+// knobs and of the sizes, kinds and types of the three steps -- never of their planes or records, so the steps are laid out over
+// none: the pipeline asks in front of the estimation, a stage entry point in front of its polynomial, and both get one answer.
+// x_dtype, x_padded, dst_dtype: as make_steps.
 // gaussians: the records are (or will be) point-symmetric Gaussians the estimation itself builds on an odd ker_size grid
-PolySpec poly_spec(pb_ctx *ctx, const ConvPass *steps, float alpha, float beta, bool gaussians) {
+PolySpec poly_spec(pb_ctx *ctx, const Geometry &g, int x_dtype, bool x_padded, int boundary, int dst_dtype, float alpha, float beta,
+                   bool gaussians) {
+    ConvPass steps[3];
+    make_steps(g, nullptr, x_dtype, x_padded, nullptr, alpha, beta, boundary, nullptr, nullptr, nullptr, dst_dtype, 0, steps);
     const int mode = pb_poly_spec_mode(ctx, steps);
     if (!mode) {
         // (the zero boundary on an image too small for the ring form, the estimation's own Gaussians: every kernel on three
         // window steps -- a fact of the call again, so the polynomial issues the wave body's three launches and nothing else)
-        if (steps[0].boundary == PB_ZERO && gaussians && ctx->poly_always && pb_poly_three_steps_ok(ctx, steps)) {
-            PolySpec ps = no_poly();
-            ps.always = 2;
-            return ps;
-        }
+        if (boundary == PB_ZERO && gaussians && ctx->poly_always && pb_poly_three_steps_ok(ctx, steps)) return window_form_spec();
         return no_poly();
     }
     // (every composite of a 25-tap kernel fits a 128 x 128 window -- halo <= 36, tile >= 56 -- so where those windows are admitted
@@ -420,10 +434,13 @@ PolySpec poly_spec(pb_ctx *ctx, const ConvPass *steps, float alpha, float beta, 
 
 // y = a3 K^3 x + a2 K^2 x + a1 K x + beta x by Horner, three stencil passes (deblurring.py:122-138).
 // X is either the un-padded image (virtual pad) or a padded fp32 image (after edgetaper).
+// plan: the pipeline's plan of this iteration; nullptr (a stage entry point): slot 0, and the polynomial's spec from poly_spec
+// here -- for records the call did not estimate itself, so nothing vouches for Gaussians
 int run_polynomial(pb_ctx *ctx, const Geometry &g, const void *xsrc, int x_dtype, const float *xpadded,
                    const pb_blur_info *info, float alpha, float beta, int boundary, float *t1, float *t2, void *dst,
-                   int dst_dtype, int clamp01) {
+                   int dst_dtype, int clamp01, const IterPlan *plan = nullptr) {
     const float a3 = alpha / 2 - beta + 2, a2 = 3 * beta - alpha - 6, a1 = 5 - 3 * beta + alpha / 2;
+    const PassWant plain{no_poly(), plan ? plan->slot : 0};
     if (g.sep1) {
         // K ~= K2 after K1 (estimate.hip: sep_records_kernel).  One launch per step keeps u = K1 * t in LDS (conv_xt.hip, the
         // --experimental build); where it is not built -- the default build, 8-bit images -- two launches through the sparse
@@ -443,22 +460,22 @@ int run_polynomial(pb_ctx *ctx, const Geometry &g, const void *xsrc, int x_dtype
                 // images whose exact kernel is rank-1 were skipped there: the exact separable body does them
                 ConvPass pe = p2;
                 pe.info = info; pe.skip_general = 1;
-                rc = pb_launch_conv(ctx, pe);
+                rc = pb_launch_conv(ctx, pe, plain);
                 if (rc) return rc;
             }
             if (rc == PB_ERR_UNSUPPORTED) {
                 if (step == 0) set_in_virtual(p1, g, xsrc, x_dtype); else set_in_padded(p1, g, tmp[step - 1]);
-                rc = pb_launch_conv(ctx, p1);
+                rc = pb_launch_conv(ctx, p1, plain);
                 if (rc) return rc;
                 set_in_padded(p2, g, g.sep_u);
-                rc = pb_launch_conv(ctx, p2);
+                rc = pb_launch_conv(ctx, p2, plain);
                 if (rc) return rc;
             }
         }
         return PB_OK;
     }
     ConvPass steps[3];
-    make_steps(g, xsrc, x_dtype, xpadded, info, alpha, beta, boundary, t1, t2, dst, dst_dtype, clamp01, steps);
+    make_steps(g, xpadded ? xpadded : xsrc, x_dtype, xpadded != nullptr, info, alpha, beta, boundary, t1, t2, dst, dst_dtype, clamp01, steps);
     if (g.big.taps) {
         for (int s = 0; s < 3; ++s) {
             const int rc = pb_launch_conv_big(ctx, steps[s], g.big);
@@ -468,12 +485,8 @@ int run_polynomial(pb_ctx *ctx, const Geometry &g, const void *xsrc, int x_dtype
     }
     // (under the wrap boundary the three steps are one filter, deblurring.py:139-169: images for which one window pass
     // with that filter's spectrum is the cheaper form take it, pb_fft_sel.poly; the spectra are then the polynomial's)
-    // (records the estimation has just built under PolySpec.always keep that spec: their spectra are already those it asks for)
-    const bool by_est = ctx->spectra.spec().always && ctx->spectra.by_estimate() && ctx->spectra.holds(info, g.B);
-    ctx->poly_want = poly_spec(ctx, steps, alpha, beta, by_est || g.est_gaussians);
-    const int rc = pb_launch_conv_poly(ctx, steps);
-    ctx->poly_want = no_poly();
-    return rc;
+    const PolySpec spec = plan ? plan->poly : poly_spec(ctx, g, x_dtype, xpadded != nullptr, boundary, dst_dtype, alpha, beta, false);
+    return pb_launch_conv_poly(ctx, steps, PassWant{spec, plain.slot});
 }
 
 // The same polynomial with the pure-phase filter in front (deblurring.py:141-169 with not_symmetric=True): one transform over
@@ -499,8 +512,9 @@ int inverse_filter(pb_ctx *ctx, const Geometry &g, const void *src, int src_dtyp
                    const pb_blur_info *info, float alpha, float beta, int boundary, int edgetaping, int remove_halo,
                    const void *g0x, const void *g0y, const float *nM, int final_clamp,
                    const void *recomb_cur = nullptr, int recomb_cur_dtype = 0, const float *recomb_smooth = nullptr,
-                   int g_dtype = PB_F32) {
+                   int g_dtype = PB_F32, const IterPlan *plan = nullptr) {
     // recomb_cur (only with remove_halo): the halo kernel also adds back the detail layer cur - recomb_smooth
+    // plan: the pipeline's plan of this iteration (nullptr: a stage entry point -- see run_polynomial)
     float *t1 = nullptr, *t2 = nullptr;
     if (!g.t1h && !(g.phase_taps && !edgetaping)) {     // (the phase polynomial has scratch of its own; the edgetaper in front of it borrows t1)
         t1 = static_cast<float *>(pb_scratch(ctx, "inv.t1", sizeof(float) * g.P * g.pplane));
@@ -512,18 +526,19 @@ int inverse_filter(pb_ctx *ctx, const Geometry &g, const void *src, int src_dtyp
         float *pa = static_cast<float *>(pb_scratch(ctx, "inv.pa", sizeof(float) * g.P * g.pplane));
         if (!pa) return PB_ERR_NOMEM;
         float *res = nullptr;
-        int rc = run_edgetaper(ctx, g, src, src_dtype, info, boundary, pa, t1, &res);   // t1 is free until the polynomial
+        const PassWant blends = plan ? PassWant{plan->blends, plan->slot} : PassWant();
+        int rc = run_edgetaper(ctx, g, src, src_dtype, info, boundary, pa, t1, &res, blends);   // t1 is free until the polynomial
         if (rc) return rc;
         xpadded = res;
     }
     if (!remove_halo)
         return g.phase_taps ? run_phase_polynomial(ctx, g, src, src_dtype, xpadded, alpha, beta, dst, dst_dtype, final_clamp)
                             : run_polynomial(ctx, g, src, src_dtype, xpadded, info, alpha, beta, boundary, t1, t2, dst, dst_dtype,
-                                             final_clamp);
+                                             final_clamp, plan);
     float *y = static_cast<float *>(pb_scratch(ctx, "inv.y", sizeof(float) * g.P * g.HW));
     if (!y) return PB_ERR_NOMEM;
     int rc = g.phase_taps ? run_phase_polynomial(ctx, g, src, src_dtype, xpadded, alpha, beta, y, PB_F32, 0)
-                          : run_polynomial(ctx, g, src, src_dtype, xpadded, info, alpha, beta, boundary, t1, t2, y, PB_F32, 0);
+                          : run_polynomial(ctx, g, src, src_dtype, xpadded, info, alpha, beta, boundary, t1, t2, y, PB_F32, 0, plan);
     if (rc) return rc;
     if (!g0x) {
         // grad_img=None (deblurring.py:200-201): the gradients of the image the halo mask blends with -- the crop of the
@@ -577,7 +592,7 @@ int pb_estimate_blur(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H
     if (!in || !opt || !dev_info) return pb_fail(ctx, PB_ERR_BADARG, "null argument");
     PB_HIP(hipSetDevice(ctx->device));
     pb_forget_records(ctx, dev_info, B);
-    return pb_estimate_impl(ctx, in, dtype, B, C, H, W, opt, dev_info);
+    return pb_estimate_impl(ctx, in, dtype, B, C, H, W, opt, dev_info, no_poly(), no_poly(), 0);
 }
 
 int pb_make_kernels(pb_ctx *ctx, int B, const float *host_sigma, const float *host_rho, const float *host_theta_rad,
@@ -701,7 +716,7 @@ int pb_convolve2d(pb_ctx *ctx, const float *in, float *out, int B, int C, int Hp
     ConvPass p = base_pass(g, recs, boundary);
     set_in_padded(p, g, in); set_x_padded(p, g, in); set_out_padded(p, g, out);
     p.scale = 1.f; p.coef = 0.f;
-    return pb_launch_conv(ctx, p);
+    return pb_launch_conv(ctx, p, PassWant());
 }
 
 int pb_edgetaper(pb_ctx *ctx, const float *in, float *out, int B, int C, int Hp, int Wp, const pb_blur_info *dev_info,
@@ -718,13 +733,13 @@ int pb_edgetaper(pb_ctx *ctx, const float *in, float *out, int B, int C, int Hp,
     ConvPass p = base_pass(g, recs, boundary);
     p.epilogue = EPI_TAPER;
     set_in_padded(p, g, in); set_x_padded(p, g, in); set_out_padded(p, g, out);
-    int rc = pb_launch_conv(ctx, p);
+    int rc = pb_launch_conv(ctx, p, PassWant());
     if (rc) return rc;
     set_in_padded(p, g, out); set_x_padded(p, g, out); set_out_padded(p, g, tmp);
-    rc = pb_launch_conv(ctx, p);
+    rc = pb_launch_conv(ctx, p, PassWant());
     if (rc) return rc;
     set_in_padded(p, g, tmp); set_x_padded(p, g, tmp); set_out_padded(p, g, out);
-    return pb_launch_conv(ctx, p);
+    return pb_launch_conv(ctx, p, PassWant());
 }
 
 int pb_halo_mask(pb_ctx *ctx, const float *x, const float *y, const float *grad0_x, const float *grad0_y, float *out,
@@ -819,15 +834,17 @@ int pb_polyblur_batch(pb_ctx *ctx, const void *in, void *out, int dtype, int B, 
     if (ksize > PB_KSIZE && opt->separable_approx)
         return pb_fail(ctx, PB_ERR_UNSUPPORTED, "ker_size %d: the separable approximation is built for sizes up to %d", ksize, PB_KSIZE);
     PB_HIP(hipSetDevice(ctx->device));
-    // (every iteration's choices of body keep a slot of their own; whichever way the call ends, later passes on this context
-    // read and write slot 0 again, and what one-pass spec the call asked for is forgotten)
-    struct SlotGuard { pb_ctx *c; ~SlotGuard() { c->sel_slot = 0; c->poly_want = no_poly(); c->poly_want2 = no_poly(); } } slot_guard{ctx};
-    ctx->sel_slot = 0;
     ctx->sel2_mask = 0;
     Geometry g = geometry(B, C, H, W, ksize / 2);
-    const bool poly_eligible = (opt->boundary == PB_WRAP || ctx->zero_ring) && !opt->edgetaping && !opt->separable_approx && ksize <= PB_KSIZE;
-    g.est_gaussians = (ksize & 1) && ksize <= PB_KSIZE && !opt->separable_approx;
-    g.taper_windows = opt->edgetaping && g.est_gaussians && ctx->poly_always && ctx->poly_mode != 0 && ctx->fft_min_phases >= 0 && ctx->fft_wave;
+    // the polynomial goes through pb_launch_conv_poly (a PolySpec means something to it) ...
+    const bool poly_steps = !opt->separable_approx && ksize <= PB_KSIZE;
+    // ... and the estimation builds its spectra, not the kernels' own
+    const bool poly_eligible = (opt->boundary == PB_WRAP || ctx->zero_ring) && !opt->edgetaping && poly_steps;
+    // the records are point-symmetric Gaussians the estimation of THIS call builds on an odd ker_size grid (PolySpec.always)
+    const bool est_gaussians = (ksize & 1) && poly_steps;
+    // ... and every one of them takes the window form of a single pass (PolySpec.always == 2): the edgetaper's three blends
+    // issue the wave body's launch and nothing else
+    const bool taper_windows = opt->edgetaping && est_gaussians && ctx->poly_always && ctx->poly_mode != 0 && ctx->fft_min_phases >= 0 && ctx->fft_wave;
     const long n = (long)g.P * g.HW;
     const int n_iter = opt->n_iter;
     if (n_iter == 0) {
@@ -911,38 +928,29 @@ int pb_polyblur_batch(pb_ctx *ctx, const void *in, void *out, int dtype, int B, 
         if (dtype != PB_F32 && it != n_iter - 1) dst = (it % 2 == 0) ? tmpimg : tmpimg2;
         const int cur_dtype = it == 0 ? dtype : work, dst_dtype = it == n_iter - 1 ? dtype : work;
         pb_blur_info *info = infos + (size_t)it * B;
-        ctx->sel_slot = it;                       // (this iteration's choices of body keep a slot of their own: pb_body_selection)
-        // The estimation ends with the kernels' spectra and the images' choice of body: it has to know whether this
-        // iteration's polynomial may take the one-pass form (pb_fft_sel.poly) -- exactly what run_polynomial will ask for.
-        if (poly_eligible) {
+        // The plan of the iteration.  The estimation ends with the kernels' spectra and the images' choice of body, so it has to
+        // know what the passes behind it will ask for: they are handed the same plan.
+        IterPlan plan;
+        plan.slot = it;                           // (this iteration's choices of body keep a slot of their own: pb_body_selection)
+        if (poly_steps) {
+            // (the polynomial's operand: the image or its smooth component, behind an edgetaper the padded, tapered plane; its
+            // result: fp32 wherever another kernel reads it before the iteration's last store)
             const int src_dtype = opt->prefilter != PB_PREFILTER_NONE ? PB_F32 : cur_dtype;
             const int last_out = (opt->remove_halo || opt->prefilter != PB_PREFILTER_NONE) ? PB_F32 : dst_dtype;
-            ConvPass steps[3];
-            make_steps(g, cur, src_dtype, nullptr, info, opt->alpha, opt->beta, opt->boundary, nullptr, nullptr, dst, last_out, 1, steps);
-            ctx->poly_want = poly_spec(ctx, steps, opt->alpha, opt->beta, (ksize & 1) != 0);
+            plan.poly = poly_spec(ctx, g, src_dtype, opt->edgetaping != 0, opt->boundary, last_out, opt->alpha, opt->beta, est_gaussians);
+        }
+        if (poly_eligible) {
+            plan.est1 = plan.poly;
             // (the zero boundary in its window-pass + ring form: the ring steps run with the kernels' OWN spectra -- the estimation
             // builds them as its second set instead of a khat_kernel launch in front of the ring)
-            if (opt->boundary == PB_ZERO && ctx->poly_want.always == 1) { ctx->poly_want2 = no_poly(); ctx->poly_want2.always = 2; }
+            if (opt->boundary == PB_ZERO && plan.poly.always == 1) plan.est2 = window_form_spec();
+        } else if (taper_windows) {
+            plan.blends = plan.est1 = window_form_spec();      // (the blends come first: the kernels' own spectra, window form for all)
+            // (... and the polynomial behind them wants ITS spectra: the second set.  The zero boundary's ring there would want a
+            // third set: left to its own launch)
+            if (ctx->poly_padded && opt->boundary != PB_ZERO) plan.est2 = plan.poly;
         }
-        else if (g.taper_windows) {
-            ctx->poly_want = no_poly(); ctx->poly_want.always = 2;      // (the blends come first: the kernels' own spectra, window form for all)
-            // (... and the polynomial behind them wants ITS spectra: the second set, under the spec run_polynomial will ask for --
-            // its source is the padded, tapered plane)
-            if (ctx->poly_padded) {
-                const int src_dtype = opt->prefilter != PB_PREFILTER_NONE ? PB_F32 : cur_dtype;
-                const int last_out = (opt->remove_halo || opt->prefilter != PB_PREFILTER_NONE) ? PB_F32 : dst_dtype;
-                ConvPass steps[3];
-                float *pa = static_cast<float *>(pb_scratch(ctx, "inv.pa", sizeof(float) * g.P * g.pplane));
-                if (!pa) return PB_ERR_NOMEM;
-                make_steps(g, cur, src_dtype, pa, info, opt->alpha, opt->beta, opt->boundary, nullptr, nullptr, dst, last_out, 1, steps);
-                const PolySpec want = ctx->poly_want;
-                ctx->poly_want2 = poly_spec(ctx, steps, opt->alpha, opt->beta, true);
-                ctx->poly_want = want;
-                if (opt->boundary == PB_ZERO) ctx->poly_want2 = no_poly();      // (the ring there wants a third set: left to its own launch)
-            }
-        }
-        rc = pb_estimate_impl(ctx, cur, cur_dtype, B, C, H, W, opt, info);
-        ctx->poly_want = no_poly(); ctx->poly_want2 = no_poly();
+        rc = pb_estimate_impl(ctx, cur, cur_dtype, B, C, H, W, opt, info, plan.est1, plan.est2, plan.slot);
         if (rc) return rc;
         if (ksize > PB_KSIZE) {
             rc = pb_build_big_taps(ctx, info, B, ksize, (!(ksize & 1) && opt->boundary == PB_WRAP) ? 1 : 0, &g.big);
@@ -954,7 +962,7 @@ int pb_polyblur_batch(pb_ctx *ctx, const void *in, void *out, int dtype, int B, 
         }
         if (opt->prefilter == PB_PREFILTER_NONE) {
             rc = inverse_filter(ctx, g, cur, cur_dtype, dst, dst_dtype, info, opt->alpha, opt->beta, opt->boundary,
-                                opt->edgetaping, opt->remove_halo, g0x, g0y, nM, 1, nullptr, 0, nullptr, g_dtype);
+                                opt->edgetaping, opt->remove_halo, g0x, g0y, nM, 1, nullptr, 0, nullptr, g_dtype, &plan);
             if (rc) return rc;
         } else {
             if (opt->prefilter == PB_PREFILTER_BILATERAL)
@@ -966,11 +974,11 @@ int pb_polyblur_batch(pb_ctx *ctx, const void *in, void *out, int dtype, int B, 
             if (rc) return rc;
             if (opt->remove_halo) {                 // the halo kernel recombines as it stores: no ybuf round trip
                 rc = inverse_filter(ctx, g, smooth, PB_F32, dst, dst_dtype, info, opt->alpha, opt->beta, opt->boundary,
-                                    opt->edgetaping, 1, g0x, g0y, nM, 1, cur, cur_dtype, smooth, g_dtype);
+                                    opt->edgetaping, 1, g0x, g0y, nM, 1, cur, cur_dtype, smooth, g_dtype, &plan);
                 if (rc) return rc;
             } else {
                 rc = inverse_filter(ctx, g, smooth, PB_F32, ybuf, PB_F32, info, opt->alpha, opt->beta, opt->boundary,
-                                    opt->edgetaping, 0, g0x, g0y, nM, 1);
+                                    opt->edgetaping, 0, g0x, g0y, nM, 1, nullptr, 0, nullptr, g_dtype, &plan);
                 if (rc) return rc;
                 rc = pb_recombine(ctx, ybuf, cur, cur_dtype, smooth, dst, dst_dtype, n);
                 if (rc) return rc;
@@ -978,7 +986,6 @@ int pb_polyblur_batch(pb_ctx *ctx, const void *in, void *out, int dtype, int B, 
         }
         cur = dst;
     }
-    ctx->sel_slot = 0;
     if (host_info) {
         PB_HIP(hipMemcpyAsync(host_info, infos, sizeof(pb_blur_info) * (size_t)n_iter * B, hipMemcpyDeviceToHost, ctx->stream));
         PB_HIP(hipStreamSynchronize(ctx->stream));
@@ -1159,7 +1166,7 @@ int taps_geometry(pb_ctx *ctx, const pb_taps *t, int B, int C, int H, int W, int
     return PB_OK;
 }
 
-int taps_pass(pb_ctx *ctx, const Geometry &g, const ConvPass &p) { return g.big.taps ? pb_launch_conv_big(ctx, p, g.big) : pb_launch_conv(ctx, p); }
+int taps_pass(pb_ctx *ctx, const Geometry &g, const ConvPass &p) { return g.big.taps ? pb_launch_conv_big(ctx, p, g.big) : pb_launch_conv(ctx, p, PassWant()); }
 
 // The adjoint of a pass with an ODD-sized kernel is the same form under the same boundary with the taps reflected inside their
 // kh x kw array -- and the set already holds that orientation as the OTHER boundary's form (records: embed_taps(reflect); tables:
@@ -1440,7 +1447,7 @@ int pb_compute_polynomial_taps_backward(pb_ctx *ctx, const float *x, const float
         float *g2 = static_cast<float *>(pb_scratch(ctx, "grad.g2", bytes)), *g1 = static_cast<float *>(pb_scratch(ctx, "grad.g1", bytes));
         if (!t1 || !t2 || !g2 || !g1) return PB_ERR_NOMEM;
         ConvPass steps[3];
-        make_steps(g, x, PB_F32, x, recs, alpha, beta, boundary, t1, t2, g1, PB_F32, 0, steps);      // (steps[2], y itself, is not run)
+        make_steps(g, x, PB_F32, true, recs, alpha, beta, boundary, t1, t2, g1, PB_F32, 0, steps);      // (steps[2], y itself, is not run)
         for (int s = 0; s < 2; ++s) {
             rc = taps_pass(ctx, g, steps[s]);
             if (rc) return rc;

@@ -81,8 +81,8 @@ struct SpectraSet {
     bool holds(const void *info, int B) const { return owner && owner == info && n == B; }
     // (same_spec compares `always` too: the kernels' own spectra under always == 2 are not those under always == 0)
     bool holds(const void *info, int B, const PolySpec &s) const { return holds(info, B) && same_spec(built, s); }
-    void claim(const void *info, int B, const PolySpec &s, int sel_slot, bool by_estimate) {
-        owner = info; n = B; built = s; slot_ = sel_slot; est = by_estimate;
+    void claim(const void *info, int B, const PolySpec &s, int slot, bool by_estimate) {
+        owner = info; n = B; built = s; slot_ = slot; est = by_estimate;
     }
     void drop() { owner = nullptr; n = 0; est = false; }
     // a write into [lo, hi): a run of records that overlaps it anywhere, not only at its first record
@@ -91,7 +91,6 @@ struct SpectraSet {
         if (o && o < static_cast<const char *>(hi) && static_cast<const char *>(lo) < o + sizeof(pb_blur_info) * (size_t)n) drop();
     }
     void rebind(const void *b) { if (b != buf) { buf = b; drop(); } }      // (the scratch buffer was reallocated)
-    bool built_into(const void *b) const { return b && b == buf; }
     bool by_estimate() const { return est; }
     int slot() const { return slot_; }
     const PolySpec &spec() const { return built; }
@@ -103,6 +102,13 @@ private:
     bool est = false;
     const void *buf = nullptr;
 };
+
+// What the pass being launched wants of the spectra it meets -- an argument of the call, never state of the context: the PolySpec
+// they should be those of (no_poly(): a plain pass, the kernels' own spectra) and the slot of the selection scratch it writes to /
+// reads from (one per iteration of a pipeline call, pb_body_selection; 0 for every other call).  Host only: no kernel sees it.
+struct PassWant { PolySpec spec = no_poly(); int slot = 0; };
+// What pb_build_khat / pb_build_khat_ring hand out: the spectra, the selections, and the PolySpec they were built under
+struct Spectra { float *khat = nullptr; pb_fft_sel *sel = nullptr; PolySpec spec = no_poly(); };
 
 struct pb_ctx {
     bool prof_on = false;
@@ -144,11 +150,9 @@ struct pb_ctx {
     // are point-symmetric, or -- even ker_size -- placed per method by the parameter kernel: nothing to reflect there.)
     struct FlipSet { int B; int support; std::vector<float> taps; };
     std::map<const void *, FlipSet> flip_sets;
-    int sel_slot = 0, sel_last = 0, sel_B = 0;           // "conv.fftsel" holds PB_SEL_SLOTS runs of sel_B records: the slot passes write to / read from
-    const std::vector<pb_fft_sel> *known_sel = nullptr;   // the records of the pass being launched, where the host has them (sizes its job grid)
+    int sel_last = 0, sel_B = 0;                         // "conv.fftsel" holds PB_SEL_SLOTS runs of sel_B records: the slot the last pass wrote to / read from (PassWant.slot)
     SpectraSet spectra;                  // what "conv.khat" / "conv.fftsel" hold
-    // one-pass polynomial (env PB_POLY1): poly_want = what the call in progress wants the spectra to be those of (set around
-    // the estimation / the polynomial; off for every other pass)
+    // one-pass polynomial (env PB_POLY1; what a call then wants the spectra to be those of travels with it: PassWant.spec)
     // 0 never; 1 every eligible polynomial, host-built records included (those are then not cached); 2 (default) the
     // pipeline's: mildly blurred images -- the method's own use case -- estimate kernels like sigma 0.6 / rho 0.3 at an
     // oblique angle or the clamped isotropic 0.3 / 0.3, within the 4-sample halo (under the adaptive policy; the latter
@@ -157,13 +161,11 @@ struct pb_ctx {
     // qualifies; otherwise a composite launch is needed, which finds no work then and costs 1 % of a 4K call even on the
     // side stream (1.182 -> 1.195 ms): issued under the adaptive policy only.
     int poly_mode = 3;
-    PolySpec poly_want = no_poly();
     // A SECOND set of spectra + selections ("conv.khat2" / "conv.fftsel2"), built by the estimation beside the first where the
     // call will need both -- the zero boundary's ring steps want the kernels' own spectra next to the polynomial's, the
     // polynomial behind an edgetaper wants its own next to the kernels' -- instead of by a khat_kernel launch of its own
     // between the estimation and the pass (measured: 23 us per iteration of a 4K method='direct' call, 9 us with edgetaping).
-    // poly_want2: what the estimation in progress is asked to build there (on == 0 && always == 0: nothing).
-    PolySpec poly_want2 = no_poly();
+    // What the estimation is asked to build there is an argument of pb_estimate_impl (on == 0 && always == 0: nothing).
     SpectraSet spectra2;
     unsigned sel2_mask = 0;              // iterations (slots of "conv.fftsel2", as of "conv.fftsel") whose polynomial read the SECOND set's selections: pb_body_selection reports those
     long zero_ring_min_pairs = 4096;     // env PB_ZERO_RING_MIN_PAIRS: the window pass + border ring form of a zero-boundary polynomial only for images of at least this many three-step window pairs (40 x 40 tiles, all channels: two rounds of the chip)
@@ -295,30 +297,28 @@ struct ConvPass {
                          // the padded border depends on (conv_wfft.hip: ring_live)
 };
 
-int pb_launch_conv(pb_ctx *ctx, const ConvPass &p);
+int pb_launch_conv(pb_ctx *ctx, const ConvPass &p, const PassWant &want);
 // the three Horner steps of one polynomial (same planes, records and x operand; step s reads what step s - 1 wrote)
-int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps);
+int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps, const PassWant &want);
 int pb_launch_conv_xt(pb_ctx *ctx, const ConvPass &p);                       // conv_xt.hip
-int pb_build_khat(pb_ctx *ctx, const pb_blur_info *info, int B, float **khat, pb_fft_sel **sel, bool launch);
-int pb_build_khat_ring(pb_ctx *ctx, const pb_blur_info *info, int B, float **khat, pb_fft_sel **sel);   // conv_fft.hip: the kernels' OWN spectra, every symmetric kernel on three-step windows, in a second scratch set
-int pb_khat_buffers(pb_ctx *ctx, int B, float **khat, pb_fft_sel **sel);   // the scratch alone (the estimation fills it itself)
-int pb_khat2_buffers(pb_ctx *ctx, int B, float **khat, pb_fft_sel **sel);  // ... of the second set
-// the spec under which the spectra a pass reads were built: the second set's where the pass reads that set (the polynomial behind
-// an edgetaper, whose FIRST set holds the blends' kernels -- job lists sized from the first set's spec were too short there)
-inline const PolySpec &pb_spec_of_spectra(const pb_ctx *ctx, const void *khat) {
-    return ctx->spectra2.built_into(khat) ? ctx->spectra2.spec() : ctx->spectra.spec();
-}
+// conv_fft.hip: the spectra want.spec asks for, from either scratch set (out->spec: the spec of the set handed out)
+int pb_build_khat(pb_ctx *ctx, const pb_blur_info *info, int B, const PassWant &want, bool launch, Spectra *out);
+int pb_build_khat_ring(pb_ctx *ctx, const pb_blur_info *info, int B, const PassWant &want, Spectra *out);   // the kernels' OWN spectra, every symmetric kernel on three-step windows, in the second scratch set (want.slot alone is read)
+int pb_khat_buffers(pb_ctx *ctx, int B, const PassWant &want, float **khat, pb_fft_sel **sel);   // the scratch alone (the estimation fills it itself)
+int pb_khat2_buffers(pb_ctx *ctx, int B, const PassWant &want, float **khat, pb_fft_sel **sel);  // ... of the second set
 int pb_cache_records(pb_ctx *ctx, const pb_blur_info *info, int B);        // conv.hip: after the host (re)built these records
 void pb_forget_range(pb_ctx *ctx, const void *dst, size_t bytes);            // a write into device memory: every fact and hint about records it overlaps
 inline void pb_forget_records(pb_ctx *ctx, const void *info, int B) { pb_forget_range(ctx, info, sizeof(pb_blur_info) * (size_t)B); }   // B records at info are about to be rewritten
 void pb_forget_hints(pb_ctx *ctx);                                           // the record cache and both spectra sets (flip_sets are facts: by range only)
 int pb_launch_conv_fft(pb_ctx *ctx, const ConvPass &p);
 int pb_launch_conv_strip(pb_ctx *ctx, const ConvPass &p);                    // conv_strip.hip; PB_ERR_UNSUPPORTED: not an all-fp32 plain Horner pass
-int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p);                     // conv_wfft.hip; PB_ERR_UNSUPPORTED: dtype combination not built
+// spec: the PolySpec p.khat was built under (Spectra.spec).  known: the records' selections where the host has read them -- the job
+// grid is then exactly this launch's jobs --, nullptr where it has not: the grid is the longest list the spec admits
+int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known);   // conv_wfft.hip; PB_ERR_UNSUPPORTED: dtype combination not built
 bool pb_conv_fft_types(const ConvPass &p);                                   // conv_fft.hip: whether the workgroup form is built for the pass's types
 bool pb_conv_wfft_types(const ConvPass &p);
-int pb_launch_conv_w128(pb_ctx *ctx, const ConvPass &p);                     // conv_w128.hip: the one-pass polynomial on 128 x 128 windows (pb_fft_sel.poly == 2)
-int pb_launch_conv_win(pb_ctx *ctx, const ConvPass &p);                      // conv_win.hip: the one window pass of every image, 128 x 128 or 64-wide windows by its record, in ONE launch; PB_ERR_UNSUPPORTED: types not built
+int pb_launch_conv_w128(pb_ctx *ctx, const ConvPass &p, const std::vector<pb_fft_sel> *known);   // conv_w128.hip: the one-pass polynomial on 128 x 128 windows (pb_fft_sel.poly == 2)
+int pb_launch_conv_win(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known);   // conv_win.hip: the one window pass of every image, 128 x 128 or 64-wide windows by its record, in ONE launch; PB_ERR_UNSUPPORTED: types not built
 bool pb_conv_win_types(const ConvPass &p);                                   // ... whether it is built for this composite pass
 bool pb_conv_w128_feasible(const ConvPass &p);                               // ... and whether its worst-case job list fits the grid
 bool pb_conv_wfft_feasible(const ConvPass &p, bool poly2);                   // conv_wfft.hip: likewise for the wave form
@@ -364,8 +364,10 @@ int pb_tap_gradient_groups(int B, int C, int H, int W);
 // estimation (estimate.hip)
 // ------------------------------------------------------------------------------------
 constexpr int kMaxLineLength = 65536;          // longest line of the spectral derivative (pb_fft_length_supported, estimate.hip)
+// spec1 / spec2: the PolySpec the spectra the estimation builds into the first / second scratch set are those of (spec2 with
+// on == 0 && always == 0: no second set); slot: the slot of the selection scratch they go to (PassWant)
 int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H, int W,
-                     const pb_options *opt, pb_blur_info *dev_info);
+                     const pb_options *opt, pb_blur_info *dev_info, const PolySpec &spec1, const PolySpec &spec2, int slot);
 int pb_make_sep_records(pb_ctx *ctx, int B, const pb_blur_info *dev_info, pb_blur_info *sep, int support, int ksize);
 int pb_kernel_size(const pb_options *opt);      // validated ker_size (2 .. PB_KSIZE_MAX; above PB_KSIZE: conv_big.hip's path); 0 if unsupported
 int pb_fourier_gradients_impl(pb_ctx *ctx, const float *planes, int P, int H, int W, float *gx, float *gy);

@@ -324,7 +324,7 @@ int launch_typed(pb_ctx *ctx, const ConvPass &p) {
 // One launch per pass: each image's record decides on the device which body evaluates its tiles, so a batch
 // may mix rank-1 and general kernels and the host never has to read the estimates back.
 static int launch_stencil(pb_ctx *ctx, const ConvPass &p);
-static int launch_tile_spectrum(pb_ctx *ctx, const ConvPass &p);
+static int launch_tile_spectrum(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known);
 
 // Dense kernels above the context's phase threshold take the tile-spectrum body: a second launch of the same step, in
 // which -- as in the first -- every image's tiles exit at once unless the image's record selects that body.  For record
@@ -337,13 +337,14 @@ static bool fft_pass_ok(const ConvPass &p) {
            pb_conv_fft_feasible(p);
 }
 
-// What the host knows about the B records at `info` under the spec the pass in progress wants (ctx->poly_want): nullptr =
-// nothing -- records built on the device, or a one-pass spec these records have not met yet.
-static const pb_ctx::BodyFlags *known_flags(pb_ctx *ctx, const void *info, int B, const std::vector<pb_fft_sel> **sel = nullptr) {
+// What the host knows about the B records at `info` under the spec the pass wants: nullptr = nothing -- records built on the
+// device, or a one-pass spec these records have not met yet.
+static const pb_ctx::BodyFlags *known_flags(pb_ctx *ctx, const void *info, int B, const PassWant &want,
+                                            const std::vector<pb_fft_sel> **sel = nullptr) {
     const auto it = ctx->rec_cache.find(info);
     if (it == ctx->rec_cache.end() || it->second.B != B) return nullptr;
-    if (!ctx->poly_want.on) { if (sel) *sel = nullptr; return &it->second.plain; }
-    if (!it->second.poly_valid || !same_spec(it->second.spec, ctx->poly_want)) return nullptr;
+    if (!want.spec.on) { if (sel) *sel = nullptr; return &it->second.plain; }
+    if (!it->second.poly_valid || !same_spec(it->second.spec, want.spec)) return nullptr;
     if (sel) *sel = &it->second.sel;
     return &it->second.poly;
 }
@@ -356,23 +357,23 @@ static pb_ctx::BodyFlags flags_of(const std::vector<pb_fft_sel> &h) {
     return f;
 }
 
-int pb_launch_conv(pb_ctx *ctx, const ConvPass &p0) {
+int pb_launch_conv(pb_ctx *ctx, const ConvPass &p0, const PassWant &want) {
     ConvPass p = p0;
     bool fft = ctx->fft_min_phases >= 0 && !p.no_fft && fft_pass_ok(p);
     const int B = p.P / p.C;
     const std::vector<pb_fft_sel> *ksel = nullptr;
-    const pb_ctx::BodyFlags *kf = known_flags(ctx, p.info, B, &ksel);
+    const pb_ctx::BodyFlags *kf = known_flags(ctx, p.info, B, want, &ksel);
     const bool have = kf != nullptr;
     // (a step of a polynomial whose one-pass images another launch does: only the images that go step by step count)
-    if (fft && have && !(ctx->poly_want.on && p.poly == 0 ? kf->any_fft3 : kf->any_fft)) fft = false;
+    if (fft && have && !(want.spec.on && p.poly == 0 ? kf->any_fft3 : kf->any_fft)) fft = false;
     p.fsel = nullptr; p.khat = nullptr;
-    if (fft || (have && ctx->poly_want.on)) {
-        float *k = nullptr; pb_fft_sel *s = nullptr;
+    Spectra sp;
+    if (fft || (have && want.spec.on)) {
         // (spectra an earlier pass built count only while the scratch still holds them for these records)
         const bool built = (p.khat_ready || have || ctx->spectra.by_estimate()) && ctx->spectra.holds(p.info, B);   // (pb_build_khat also rebuilds spectra of another PolySpec)
-        const int rc = pb_build_khat(ctx, p.info, B, &k, &s, !built);
+        const int rc = pb_build_khat(ctx, p.info, B, want, !built, &sp);
         if (rc) return rc;
-        p.khat = k; p.fsel = s;      // (the stencil bodies read the selection too: they skip the one-pass images)
+        p.khat = sp.khat; p.fsel = sp.sel;      // (the stencil bodies read the selection too: they skip the one-pass images)
     } else if (!p.khat_ready && !have) {
         ctx->spectra.drop();     // device-built records took a pass without spectra: whatever the scratch holds is not theirs
     }
@@ -393,7 +394,7 @@ int pb_launch_conv(pb_ctx *ctx, const ConvPass &p0) {
     (void)strip;
 #endif
     // (PolySpec.always == 2, records of the estimation: every image takes the window form -- no stencil launch to find that out)
-    const bool windows_only = !have && fft && !ctx->poly_want.on && ctx->poly_want.always == 2 && ctx->fft_wave && pb_conv_wfft_types(p) &&
+    const bool windows_only = !have && fft && !want.spec.on && want.spec.always == 2 && ctx->fft_wave && pb_conv_wfft_types(p) &&
                               pb_conv_wfft_feasible(p, false);
     const bool tile_needed = windows_only ? false : (!have || (strip_done ? kf->any_tile : kf->any_other));
     if (tile_needed) {
@@ -401,21 +402,18 @@ int pb_launch_conv(pb_ctx *ctx, const ConvPass &p0) {
         if (rc) return rc;
     }
     if (!fft) return PB_OK;
-    ctx->known_sel = ksel;
-    const int rc = launch_tile_spectrum(ctx, p);
-    ctx->known_sel = nullptr;
-    return rc;
+    return launch_tile_spectrum(ctx, p, sp.spec, ksel);
 }
 
 // the tile-spectrum launch of a pass: the wave form where it is built and worth it, else the workgroup form -- which cannot
 // run one-pass images whose composite halo is beyond its classes (PolySpec.on == 2 is only asked for where the wave form
-// takes every launch, pb_poly_spec)
-static int launch_tile_spectrum(pb_ctx *ctx, const ConvPass &p) {
+// takes every launch, pb_poly_spec).  spec: what p.khat was built under; known: the records where the host has read them
+static int launch_tile_spectrum(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known) {
     if (ctx->fft_wave) {
-        const int rc = pb_launch_conv_wfft(ctx, p);
+        const int rc = pb_launch_conv_wfft(ctx, p, spec, known);
         if (rc != PB_ERR_UNSUPPORTED) return rc;
     }
-    if (p.poly != 0 && pb_spec_of_spectra(ctx, p.khat).on >= 2)
+    if (p.poly != 0 && spec.on >= 2)
         return pb_fail(ctx, PB_ERR_UNSUPPORTED, "one-pass polynomial with per-axis halos: the wave form does not take this pass");
     return pb_launch_conv_fft(ctx, p);
 }
@@ -511,7 +509,8 @@ struct SideStream {
 // thousand workgroups that leave at once, 6 us each on the critical path.  The two kernels of a step touch different
 // images, so the stencil bodies' three launches go to the context's side stream -- forked behind the spectra, joined
 // before the call returns -- and run (or evaporate) beside the tile-spectrum launches instead of between them.
-int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
+int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps, const PassWant &want) {
+    const PolySpec &spec = want.spec;
     bool fft = ctx->fft_min_phases >= 0;
     for (int s = 0; s < 3; ++s) fft = fft && fft_pass_ok(steps[s]);
     const pb_blur_info *info = steps[0].info;
@@ -521,19 +520,22 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
     // every later polynomial on them issues exactly the launches it needs, with job grids of exactly the size it needs.
     {
         const auto known = ctx->rec_cache.find(info);
-        if (fft && ctx->poly_want.on && known != ctx->rec_cache.end() && known->second.B == B &&
-            !(known->second.poly_valid && same_spec(known->second.spec, ctx->poly_want))) {
-            float *k0 = nullptr; pb_fft_sel *s0 = nullptr;
-            int rc0 = pb_build_khat(ctx, info, B, &k0, &s0, true);
+        if (fft && spec.on && known != ctx->rec_cache.end() && known->second.B == B &&
+            !(known->second.poly_valid && same_spec(known->second.spec, spec))) {
+            Spectra s0;
+            int rc0 = pb_build_khat(ctx, info, B, want, true, &s0);
             if (rc0) return rc0;
             std::vector<pb_fft_sel> h((size_t)B);
-            PB_HIP(hipMemcpyAsync(h.data(), s0, sizeof(pb_fft_sel) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+            PB_HIP(hipMemcpyAsync(h.data(), s0.sel, sizeof(pb_fft_sel) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
             PB_HIP(hipStreamSynchronize(ctx->stream));
             pb_ctx::RecFlags &rf = known->second;
-            rf.poly_valid = true; rf.spec = ctx->poly_want; rf.poly = flags_of(h); rf.sel = h;
+            rf.poly_valid = true; rf.spec = spec; rf.poly = flags_of(h); rf.sel = h;
         }
     }
-    const bool have = known_flags(ctx, info, B) != nullptr;
+    // (what the host has read of these records under the spec: their flags, and their selections -- ksel -- for exact job grids)
+    const std::vector<pb_fft_sel> *ksel = nullptr;
+    const pb_ctx::BodyFlags *kf = known_flags(ctx, info, B, want, &ksel);
+    const bool have = kf != nullptr;
     // (records the estimation has just built bring their spectra with them: blur_params_kernel ends with them)
     const bool held = ctx->spectra.holds(info, B), by_estimate = held && ctx->spectra.by_estimate();
     // (per-launch profiling keeps everything on one stream: events on the side stream would time its launches' wait
@@ -541,46 +543,40 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
     // One-pass polynomial: the images whose spectrum is the polynomial's take ONE window pass from the first step's input
     // to the last step's output; the later steps' launches skip them.  When the first and the last step store the same
     // type, the first step's launch takes them along (ConvPass.poly = 2: no launch of their own, nothing to pay when no
-    // image qualifies); otherwise a composite launch does them.  (The spectra the steps meet are those ctx->poly_want
+    // image qualifies); otherwise a composite launch does them.  (The spectra the steps meet are those `want.spec`
     // asks for: pb_build_khat rebuilds any others.)
     // PolySpec.always == 2 (records of the estimation): every image on three window steps, three launches of the wave body
-    if (fft && !ctx->poly_want.on && ctx->poly_want.always == 2 && !have) {
-        float *k = nullptr; pb_fft_sel *sel = nullptr;
-        int rc = pb_build_khat(ctx, info, B, &k, &sel, !by_estimate);
+    if (fft && !spec.on && spec.always == 2 && !have) {
+        Spectra sp;
+        int rc = pb_build_khat(ctx, info, B, want, !by_estimate, &sp);
         for (int s = 0; s < 3 && !rc; ++s) {
             ConvPass p = steps[s];
-            p.khat = k; p.fsel = sel; p.poly = 0;
-            rc = pb_launch_conv_wfft(ctx, p);
+            p.khat = sp.khat; p.fsel = sp.sel; p.poly = 0;
+            rc = pb_launch_conv_wfft(ctx, p, sp.spec, nullptr);
             if (rc == PB_ERR_UNSUPPORTED) rc = pb_fail(ctx, PB_ERR_UNSUPPORTED, "three window steps: the wave form does not take this pass");
         }
         return rc;
     }
-    const bool poly_on = fft && ctx->poly_want.on;
+    const bool poly_on = fft && spec.on;
     const bool fold = poly_on && steps[0].out_dtype == steps[2].out_dtype;
     const ConvPass whole = composite_pass(steps);
+    auto with_spectra = [](ConvPass p, const Spectra &sp) { p.khat = sp.khat; p.fsel = sp.sel; return p; };
     auto first_step = [&](ConvPass &p) {
         if (!fold) return;
         p.poly = 2;
         p.out2 = whole.out; p.out2_kind = whole.out_kind; p.out2_pitch = whole.out_pitch; p.out2_plane = whole.out_plane;
         p.clamp2 = whole.clamp01;
     };
-    auto composite = [&](float *k, pb_fft_sel *sel) -> int {
-        ConvPass pc = whole;
-        pc.khat = k; pc.fsel = sel;
+    // (the composite launch sizes its grid for the longest job list the spectra's spec admits, whatever the host has read)
+    auto composite = [&](const Spectra &sp) -> int {
+        const ConvPass pc = with_spectra(whole, sp);
         if (!fft_pass_ok(pc)) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "one-pass polynomial: composite pass not feasible");
-        return launch_tile_spectrum(ctx, pc);
+        return launch_tile_spectrum(ctx, pc, sp.spec, nullptr);
     };
     // the images whose one pass runs on 128 x 128 windows (pb_fft_sel.poly == 2): a launch of their own, beside the others
-    auto composite128 = [&](float *k, pb_fft_sel *sel) -> int {
-        if (ctx->poly_want.on != 3) return PB_OK;
-        ConvPass pc = whole;
-        pc.khat = k; pc.fsel = sel;
-        const std::vector<pb_fft_sel> *ksel = nullptr;
-        (void)known_flags(ctx, info, B, &ksel);
-        ctx->known_sel = ksel;
-        const int rc = pb_launch_conv_w128(ctx, pc);
-        ctx->known_sel = nullptr;
-        return rc;
+    auto composite128 = [&](const Spectra &sp) -> int {
+        if (spec.on != 3) return PB_OK;
+        return pb_launch_conv_w128(ctx, with_spectra(whole, sp), ksel);
     };
     // The side stream pays where the launches that may find no work are expensive -- one workgroup per 64 x 64 tile of every
     // plane: 6 us at 4K, 33 us for 32 x 1080p -- against two queue-to-queue waits per polynomial (~5 - 8 us each); a single
@@ -589,28 +585,26 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
     // PolySpec.always (records of the estimation, nothing the host has read back): every image takes one window pass, on 64 x 64
     // or on 128 x 128 windows -- one launch on the caller's stream whose workgroups run either body (two launches, each skipping
     // the other's images, before conv_win.hip: the empty one cost a 4K call 3.5 - 5.8 us per iteration), and nothing else.
-    if (poly_on && ctx->poly_want.always && !have) {
-        float *k = nullptr; pb_fft_sel *sel = nullptr;
-        int rc = pb_build_khat(ctx, info, B, &k, &sel, !by_estimate);
+    if (poly_on && spec.always && !have) {
+        Spectra sp;
+        int rc = pb_build_khat(ctx, info, B, want, !by_estimate, &sp);
         if (rc) return rc;
         auto window_pass = [&]() -> int {
             // one launch carries both window forms (conv_win.hip) where it is built for the composite's types; PB_POLY_ONE_LAUNCH=0,
             // or types it is not built for: the two launches, each skipping the other's images
-            if (ctx->poly_one_launch && ctx->fft_wave && ctx->poly_want.on == 3) {
-                ConvPass pc = whole;
-                pc.khat = k; pc.fsel = sel;
+            if (ctx->poly_one_launch && ctx->fft_wave && spec.on == 3) {
+                const ConvPass pc = with_spectra(whole, sp);
                 if (pb_conv_win_types(pc)) {
                     if (!fft_pass_ok(pc)) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "one-pass polynomial: composite pass not feasible");
-                    return pb_launch_conv_win(ctx, pc);
+                    return pb_launch_conv_win(ctx, pc, sp.spec, nullptr);
                 }
             }
-            const int e = composite128(k, sel);
+            const int e = composite128(sp);
             if (e) return e;
-            if (pb_conv_wfft_types(whole)) return composite(k, sel);
-            ConvPass p = steps[0];                           // (the composite's types are not built: the first step's launch takes them along)
-            p.khat = k; p.fsel = sel;
+            if (pb_conv_wfft_types(whole)) return composite(sp);
+            ConvPass p = with_spectra(steps[0], sp);         // (the composite's types are not built: the first step's launch takes them along)
             first_step(p);
-            return launch_tile_spectrum(ctx, p);
+            return launch_tile_spectrum(ctx, p, sp.spec, nullptr);
         };
         if (steps[0].boundary != PB_ZERO) return window_pass();
         // The zero boundary: the window pass is the polynomial of the zero-EXTENDED image, which is the three-step result
@@ -620,19 +614,19 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
         // frame's tiles of the output.  A ring step is a race of single window pairs (one or two rounds of ~20 us whatever
         // its size), so the first two -- which touch neither the output nor the first set of spectra -- run on the side
         // stream BESIDE the window pass; only the third waits for both.
-        float *k2 = nullptr; pb_fft_sel *sel2 = nullptr;
+        Spectra ring;
         auto ring_steps = [&](int s0, int s1) -> int {
             int e = PB_OK;
             for (int s = s0; s < s1 && !e; ++s) {
-                ConvPass p = steps[s];
-                p.khat = k2; p.fsel = sel2; p.ring = s + 1; p.poly = 0;
-                e = pb_launch_conv_wfft(ctx, p);
+                ConvPass p = with_spectra(steps[s], ring);
+                p.ring = s + 1; p.poly = 0;
+                e = pb_launch_conv_wfft(ctx, p, ring.spec, nullptr);
                 if (e == PB_ERR_UNSUPPORTED) e = pb_fail(ctx, PB_ERR_UNSUPPORTED, "zero-boundary ring: the wave form does not take this pass");
             }
             return e;
         };
         auto first_two = [&]() -> int {
-            const int e = pb_build_khat_ring(ctx, info, B, &k2, &sel2);
+            const int e = pb_build_khat_ring(ctx, info, B, want, &ring);
             return e ? e : ring_steps(0, 2);
         };
         if (ctx->aux && !ctx->prof_on) {
@@ -650,31 +644,25 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
     }
     // Lab switch of tools/one_launch_timing.py (PB_POLY_ONE_LAUNCH=2): host-built records whose every image takes one window pass
     // go through the merged launch too, with the exact grid -- what the pipeline's launch costs, without the estimation around it.
-    if (poly_on && have && ctx->poly_one_launch == 2 && ctx->fft_wave && ctx->poly_want.on == 3 && steps[0].boundary != PB_ZERO) {
-        const std::vector<pb_fft_sel> *ksel = nullptr;
-        const pb_ctx::BodyFlags *kf = known_flags(ctx, info, B, &ksel);
-        if (kf && ksel && kf->any_fft && !kf->any_other && !kf->any_fft3 && pb_conv_win_types(whole)) {
-            ConvPass pc = whole;
-            float *k = nullptr; pb_fft_sel *sel = nullptr;
-            int rc = pb_build_khat(ctx, info, B, &k, &sel, !held);
+    if (poly_on && have && ctx->poly_one_launch == 2 && ctx->fft_wave && spec.on == 3 && steps[0].boundary != PB_ZERO) {
+        if (ksel && kf->any_fft && !kf->any_other && !kf->any_fft3 && pb_conv_win_types(whole)) {
+            Spectra sp;
+            const int rc = pb_build_khat(ctx, info, B, want, !held, &sp);
             if (rc) return rc;
-            pc.khat = k; pc.fsel = sel;
+            const ConvPass pc = with_spectra(whole, sp);
             if (!fft_pass_ok(pc)) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "one-pass polynomial: composite pass not feasible");
-            ctx->known_sel = ksel;
-            rc = pb_launch_conv_win(ctx, pc);
-            ctx->known_sel = nullptr;
-            return rc;
+            return pb_launch_conv_win(ctx, pc, sp.spec, ksel);
         }
     }
     constexpr long min_side_tiles = 12288;      // (a 4K image has 6405 stencil tiles, 32 x 1080p 53568)
     const long stencil_tiles = (long)((steps[0].H + 2 * steps[0].pad + 63) / 64) * ((steps[0].W + 2 * steps[0].pad + 63) / 64) * steps[0].P;
     const bool side_pays = ctx->aux && stencil_tiles >= min_side_tiles;
     if (!fft || have || !side_pays || ctx->prof_on) {
-        if (fft && ctx->poly_want.on == 3) {
-            float *k = nullptr; pb_fft_sel *sel = nullptr;
-            int rc = pb_build_khat(ctx, info, B, &k, &sel, !(held && (have || by_estimate)));
+        if (fft && spec.on == 3) {
+            Spectra sp;
+            int rc = pb_build_khat(ctx, info, B, want, !(held && (have || by_estimate)), &sp);
             if (rc) return rc;
-            rc = composite128(k, sel);
+            rc = composite128(sp);
             if (rc) return rc;
         }
         for (int s = 0; s < 3; ++s) {
@@ -682,33 +670,31 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
             p.khat_ready = s > 0;
             if (!fft) p.no_fft = 1;
             if (s == 0) first_step(p);
-            const int rc = pb_launch_conv(ctx, p);
+            const int rc = pb_launch_conv(ctx, p, want);
             if (rc) return rc;
         }
         if (poly_on && !fold) {
             // (the spectra the three steps have just used -- the first set's, or the second's behind an edgetaper -- and the spec they
             // were built under: images with a one-pass record wait for this launch)
-            float *k = nullptr; pb_fft_sel *sel = nullptr;
-            const int rc = pb_build_khat(ctx, info, B, &k, &sel, false);
-            if (rc) return rc;
-            if (pb_spec_of_spectra(ctx, k).on) return composite(k, sel);
+            Spectra sp;
+            const int rc = pb_build_khat(ctx, info, B, want, false, &sp);
+            return rc ? rc : composite(sp);
         }
         return PB_OK;
     }
-    float *k = nullptr; pb_fft_sel *sel = nullptr;
-    int rc = pb_build_khat(ctx, info, B, &k, &sel, !by_estimate);
+    Spectra sp;
+    int rc = pb_build_khat(ctx, info, B, want, !by_estimate, &sp);
     if (rc) return rc;
     // Which launches stay on the caller's stream: those that probably do the work -- crossing to the side stream and back
     // costs two queue-to-queue waits (~5 us each) on the critical path.  Where the spec admits 128 x 128 windows that is the
     // 128 x 128 launch, and the wave body's three launches join the stencil launches on the side stream; otherwise the wave body's.
-    const bool w128_main = poly_on && ctx->poly_want.on == 3;
+    const bool w128_main = poly_on && spec.on == 3;
     auto wave_steps = [&]() -> int {
         int e = PB_OK;
         for (int s = 0; s < 3 && !e; ++s) {
-            ConvPass p = steps[s];
-            p.khat = k; p.fsel = sel;
+            ConvPass p = with_spectra(steps[s], sp);
             if (s == 0) first_step(p);
-            e = launch_tile_spectrum(ctx, p);
+            e = launch_tile_spectrum(ctx, p, sp.spec, nullptr);
         }
         return e;
     };
@@ -716,16 +702,12 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
     PB_HIP(side.forked);
     rc = side.run([&]() -> int {
         // (the composite pass touches other images than the steps' launches do: it, too, runs -- or finds no work -- beside them)
-        int e = poly_on && !fold ? composite(k, sel) : PB_OK;
+        int e = poly_on && !fold ? composite(sp) : PB_OK;
         if (w128_main && !e) e = wave_steps();
-        for (int s = 0; s < 3 && !e; ++s) {
-            ConvPass p = steps[s];
-            p.khat = k; p.fsel = sel;
-            e = launch_stencil(ctx, p);
-        }
+        for (int s = 0; s < 3 && !e; ++s) e = launch_stencil(ctx, with_spectra(steps[s], sp));
         return e;
     });
-    if (!rc) rc = w128_main ? composite128(k, sel) : wave_steps();
+    if (!rc) rc = w128_main ? composite128(sp) : wave_steps();
     PB_HIP(side.join());
     return rc;
 }
@@ -735,11 +717,11 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps) {
 int pb_cache_records(pb_ctx *ctx, const pb_blur_info *info, int B) {
     pb_forget_records(ctx, info, B);
     if (ctx->fft_min_phases < 0) return PB_OK;
-    float *k = nullptr; pb_fft_sel *s = nullptr;
-    int rc = pb_build_khat(ctx, info, B, &k, &s, true);
+    Spectra sp;
+    int rc = pb_build_khat(ctx, info, B, PassWant(), true, &sp);       // (the kernels' own spectra: the choice of body of every single pass)
     if (rc) return rc;
     std::vector<pb_fft_sel> h(B);
-    PB_HIP(hipMemcpyAsync(h.data(), s, sizeof(pb_fft_sel) * B, hipMemcpyDeviceToHost, ctx->stream));
+    PB_HIP(hipMemcpyAsync(h.data(), sp.sel, sizeof(pb_fft_sel) * B, hipMemcpyDeviceToHost, ctx->stream));
     PB_HIP(hipStreamSynchronize(ctx->stream));
     pb_ctx::RecFlags f;
     f.B = B; f.plain = flags_of(h); f.poly_valid = false; f.spec = no_poly();

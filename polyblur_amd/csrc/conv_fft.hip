@@ -334,64 +334,68 @@ int launch_fft_typed(pb_ctx *ctx, const ConvPass &p) {
 }  // namespace
 
 // Spectra + per-image body selection for the B images of `info` (B = P / C).
-int pb_khat_buffers(pb_ctx *ctx, int B, float **khat, pb_fft_sel **sel) {
+int pb_khat_buffers(pb_ctx *ctx, int B, const PassWant &want, float **khat, pb_fft_sel **sel) {
     float *k = static_cast<float *>(pb_scratch(ctx, "conv.khat", sizeof(float) * PB_KHAT_STRIDE * (size_t)B));
-    // (one slot of selections per iteration of the call in progress, so that pb_body_selection can report every iteration's)
+    // (one slot of selections per iteration of a pipeline call, so that pb_body_selection can report every iteration's)
     pb_fft_sel *s = static_cast<pb_fft_sel *>(pb_scratch(ctx, "conv.fftsel", sizeof(pb_fft_sel) * (size_t)B * PB_SEL_SLOTS));
     if (!k || !s) return PB_ERR_NOMEM;
-    s += (size_t)(ctx->sel_slot % PB_SEL_SLOTS) * B;
-    ctx->sel_B = B; ctx->sel_last = ctx->sel_slot;
+    s += (size_t)(want.slot % PB_SEL_SLOTS) * B;
+    ctx->sel_B = B; ctx->sel_last = want.slot;
+    // (whoever is handed this slot of the FIRST set writes or reads it: the slot is no longer one whose pass read the second set's
+    // -- pb_build_khat says so again where it hands that set out.  Without this a plain pass behind a pipeline call with an
+    // edgetaper had pb_body_selection(-1) report that call's selections for it)
+    ctx->sel2_mask &= ~(1u << (want.slot % PB_SEL_SLOTS));
     ctx->spectra.rebind(k);
     *khat = k; *sel = s;
     return PB_OK;
 }
 
-int pb_khat2_buffers(pb_ctx *ctx, int B, float **khat, pb_fft_sel **sel) {
+int pb_khat2_buffers(pb_ctx *ctx, int B, const PassWant &want, float **khat, pb_fft_sel **sel) {
     float *k = static_cast<float *>(pb_scratch(ctx, "conv.khat2", sizeof(float) * PB_KHAT_STRIDE * (size_t)B));
     pb_fft_sel *s = static_cast<pb_fft_sel *>(pb_scratch(ctx, "conv.fftsel2", sizeof(pb_fft_sel) * (size_t)B * PB_SEL_SLOTS));
     if (!k || !s) return PB_ERR_NOMEM;
-    s += (size_t)(ctx->sel_slot % PB_SEL_SLOTS) * B;          // (one slot per iteration, as pb_khat_buffers)
+    s += (size_t)(want.slot % PB_SEL_SLOTS) * B;              // (one slot per iteration, as pb_khat_buffers)
     ctx->spectra2.rebind(k);
     *khat = k; *sel = s;
     return PB_OK;
 }
-int pb_build_khat(pb_ctx *ctx, const pb_blur_info *info, int B, float **khat, pb_fft_sel **sel, bool launch) {
+int pb_build_khat(pb_ctx *ctx, const pb_blur_info *info, int B, const PassWant &want, bool launch, Spectra *out) {
     float *k = nullptr; pb_fft_sel *s = nullptr;
-    const int rcb = pb_khat_buffers(ctx, B, &k, &s);
+    const int rcb = pb_khat_buffers(ctx, B, want, &k, &s);
     if (rcb) return rcb;
     // (spectra of other records, of fewer records than this pass covers, or of the kernel where the pass wants the polynomial's)
     // (... or selections written to another slot than the one this pass reads)
     // (the estimation may have built what this pass wants into the SECOND set: the polynomial behind an edgetaper)
-    const int slot = ctx->sel_slot % PB_SEL_SLOTS;
-    const bool held = ctx->spectra.holds(info, B, ctx->poly_want);
-    if (!held && ctx->poly_want.on != 0 && ctx->spectra2.holds(info, B, ctx->poly_want)) {
+    const int slot = want.slot % PB_SEL_SLOTS;
+    const bool held = ctx->spectra.holds(info, B, want.spec);
+    if (!held && want.spec.on != 0 && ctx->spectra2.holds(info, B, want.spec)) {
         float *k2 = nullptr; pb_fft_sel *s2 = nullptr;
-        const int rc2 = pb_khat2_buffers(ctx, B, &k2, &s2);
+        const int rc2 = pb_khat2_buffers(ctx, B, want, &k2, &s2);
         if (rc2) return rc2;
-        if (ctx->spectra2.holds(info, B, ctx->poly_want)) {      // (still: the scratch may have moved)
+        if (ctx->spectra2.holds(info, B, want.spec)) {           // (still: the scratch may have moved)
             ctx->sel2_mask |= 1u << slot;
-            *khat = k2; *sel = s2;
+            *out = Spectra{k2, s2, ctx->spectra2.spec()};
             return PB_OK;
         }
     }
     if (!held || ctx->spectra.slot() != slot) launch = true;
     if (launch) {
-        ctx->spectra.claim(info, B, ctx->poly_want, slot, false);
+        ctx->spectra.claim(info, B, want.spec, slot, false);
         ProfScope prof(ctx, PB_PROF_PARAMS);
         hipLaunchKernelGGL(khat_kernel, dim3((unsigned)B, KH_SLICES), dim3(KH_NT), 0, ctx->stream, info, k, s, ctx->fft_min_phases,
-                           ctx->poly_want);
+                           want.spec);
         PB_LAUNCH_CHECK();
     }
-    *khat = k; *sel = s;
+    *out = Spectra{k, s, ctx->spectra.spec()};
     return PB_OK;
 }
 
 // The kernels' own spectra (not the polynomial's) and halos in a SECOND scratch set, every point-symmetric kernel on the
 // three-step window form: what the border ring of a zero-boundary polynomial runs its three Horner steps with while the
 // first set holds the polynomial's spectra of the interior's one window pass (pb_launch_conv_poly).  One launch, not cached.
-int pb_build_khat_ring(pb_ctx *ctx, const pb_blur_info *info, int B, float **khat, pb_fft_sel **sel) {
+int pb_build_khat_ring(pb_ctx *ctx, const pb_blur_info *info, int B, const PassWant &want, Spectra *out) {
     float *k = nullptr; pb_fft_sel *s = nullptr;
-    const int rcb = pb_khat2_buffers(ctx, B, &k, &s);
+    const int rcb = pb_khat2_buffers(ctx, B, want, &k, &s);
     if (rcb) return rcb;
     PolySpec ps = no_poly();
     ps.always = 2;
@@ -399,9 +403,9 @@ int pb_build_khat_ring(pb_ctx *ctx, const pb_blur_info *info, int B, float **kha
         ProfScope prof(ctx, PB_PROF_PARAMS);
         hipLaunchKernelGGL(khat_kernel, dim3((unsigned)B, KH_SLICES), dim3(KH_NT), 0, ctx->stream, info, k, s, ctx->fft_min_phases, ps);
         PB_LAUNCH_CHECK();
-        ctx->spectra2.claim(info, B, ps, ctx->sel_slot % PB_SEL_SLOTS, false);
+        ctx->spectra2.claim(info, B, ps, want.slot % PB_SEL_SLOTS, false);
     }
-    *khat = k; *sel = s;
+    *out = Spectra{k, s, ps};
     return PB_OK;
 }
 

@@ -127,7 +127,7 @@ bool pb_conv_w128_feasible(const ConvPass &p) {
 
 // The one-pass polynomial of the images whose record selects 128 x 128 windows (pb_fft_sel.poly == 2): from the first step's
 // input to the last step's output (p: the composite pass -- scale 1, no x operand, the last step's clamp).
-int pb_launch_conv_w128(pb_ctx *ctx, const ConvPass &p) {
+int pb_launch_conv_w128(pb_ctx *ctx, const ConvPass &p, const std::vector<pb_fft_sel> *known) {
     W128Geom g;
     g.oh = (p.out_kind == OUT_INTERIOR) ? p.H : p.H + 2 * p.pad;
     g.ow = (p.out_kind == OUT_INTERIOR) ? p.W : p.W + 2 * p.pad;
@@ -140,10 +140,10 @@ int pb_launch_conv_w128(pb_ctx *ctx, const ConvPass &p) {
         const long nj = (long)(((g.ow + tx - 1) / tx + 1) / 2) * ((g.oh + ty - 1) / ty);
         return (nj + 7) / 8;
     };
-    if (ctx->known_sel) {
+    if (known) {
         long per_sum = 0;
-        for (int b = 0; b < B && b < (int)ctx->known_sel->size(); ++b) {
-            const pb_fft_sel &e = (*ctx->known_sel)[(size_t)b];
+        for (int b = 0; b < B && b < (int)known->size(); ++b) {
+            const pb_fft_sel &e = (*known)[(size_t)b];
             if (e.use_fft && e.poly == 2) per_sum += per_of(e.hx, e.hy);
         }
         if (!per_sum) return PB_OK;

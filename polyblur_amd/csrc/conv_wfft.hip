@@ -173,30 +173,27 @@ bool pb_conv_wfft_types(const ConvPass &p) {
 // whatever the size of the launch, a 512-thread workgroup ~8 us, so a three-step pass of a few hundred pairs is a race of
 // single pairs that the workgroup form used to win (700 x 500: 0.31 against 0.38 ms per call); with small images' polynomials
 // mostly one window pass now, the call is faster through this form alone (0.29 ms; 1080p 0.45 against 0.53).
-int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p) {
+int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known) {
     if (!pb_conv_wfft_types(p)) return PB_ERR_UNSUPPORTED;
-    const bool poly2 = p.poly != 0 && pb_spec_of_spectra(ctx, p.khat).on >= 2;
+    const bool poly2 = p.poly != 0 && spec.on >= 2;
     const float min_area = (float)PB_POLY_MIN_AREA;        // (the smallest one-pass tile the cost model of khat.h admits)
     WGeom g;
     long per_max = 0;
-    const bool tall = poly2 && pb_spec_of_spectra(ctx, p.khat).tall != 0;
+    const bool tall = poly2 && spec.tall != 0;
     if (!wfft_geometry(p, poly2, tall, min_area, g, per_max)) {
         if (poly2) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "conv pass: too many windows for the tile-spectrum body");
         return PB_ERR_UNSUPPORTED;
     }
     long groups = 8L * per_max * p.P;                       // list entries if every image had the smallest tiles its records may select
-    if (ctx->known_sel) {
+    if (known) {
         // the host has the records' choices (it built them): the grid is exactly the list of this launch's jobs
         const int B = p.P / p.C;
         long per_sum = 0, jobs = 0;
-        for (int b = 0; b < B && b < (int)ctx->known_sel->size(); ++b) {
-            const pb_fft_sel &e = (*ctx->known_sel)[(size_t)b];
+        for (int b = 0; b < B && b < (int)known->size(); ++b) {
+            const pb_fft_sel &e = (*known)[(size_t)b];
             const bool takes = e.use_fft && e.poly != 2 && (p.poly == 2 || (e.poly != 0) == (p.poly != 0));      // (poly_match, conv_fft_common.h)
             if (!takes) continue;
-            const bool et = tall && e.poly == 1 && e.pad_[0] != 0;      // (single windows 64 wide and 128 tall: wave_tall)
-            const int tx = FT_N - 2 * e.hx, ty = (et ? 2 * FT_N : FT_N) - 2 * e.hy;
-            const long tiles_x = (g.ow + tx - 1) / tx;
-            const long nj = (et ? tiles_x : (tiles_x + 1) / 2) * ((g.oh + ty - 1) / ty);
+            const long nj = wfft_jobs_of(g, e, tall);
             per_sum += (nj + 7) / 8; jobs += nj * p.C;
         }
         if (!jobs) return PB_OK;                            // nothing in this launch for any image

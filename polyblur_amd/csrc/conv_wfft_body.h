@@ -919,4 +919,13 @@ inline bool wfft_geometry(const ConvPass &p, bool poly2, bool tall, float min_ar
     return total > 0 && total <= (1L << 23);
 }
 
+// The jobs per plane of one image whose record `e` the host has read, as the kernels count them: window pairs, or -- `tall`, and
+// the record selects it -- single windows 64 wide and 128 tall (wave_tall)
+inline long wfft_jobs_of(const WGeom &g, const pb_fft_sel &e, bool tall) {
+    const bool et = tall && e.poly == 1 && e.pad_[0] != 0;
+    const int tx = FT_N - 2 * e.hx, ty = (et ? 2 * FT_N : FT_N) - 2 * e.hy;
+    const long tiles_x = (g.ow + tx - 1) / tx;
+    return (et ? tiles_x : (tiles_x + 1) / 2) * ((g.oh + ty - 1) / ty);
+}
+
 }  // namespace

@@ -155,11 +155,11 @@ bool pb_conv_win_types(const ConvPass &p) {
 }
 
 // The one window pass of every image of the batch, whichever form its record selects (p: the composite pass).  The grid is the
-// longer of the two forms' worst-case job lists where the host has not read the records, else (ctx->known_sel: the timing tool's
-// lab switch) exactly the images' lists.  PB_ERR_UNSUPPORTED: types not built -- the caller issues the two launches.
-int pb_launch_conv_win(pb_ctx *ctx, const ConvPass &p) {
+// longer of the two forms' worst-case job lists where the host has not read the records, else (`known`: the timing tool's
+// lab switch) exactly the images' lists.  spec: what p.khat was built under (behind an edgetaper: the second set's).
+// PB_ERR_UNSUPPORTED: types not built -- the caller issues the two launches.
+int pb_launch_conv_win(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known) {
     if (!pb_conv_win_types(p)) return PB_ERR_UNSUPPORTED;
-    const PolySpec &spec = pb_spec_of_spectra(ctx, p.khat);      // (behind an edgetaper: the second set's)
     const bool poly2 = spec.on >= 2, tall = poly2 && spec.tall != 0;
     WGeom g;
     long per_max = 0;
@@ -168,17 +168,13 @@ int pb_launch_conv_win(pb_ctx *ctx, const ConvPass &p) {
     const int B = p.P / p.C;
     const int hmax = (W_N - PB_POLY128_MIN_T) / 2;
     long groups = 8L * B * std::max(w128_per_of(g.ow, g.oh, hmax, hmax) * p.C, (per_max * p.C + 3) / 4);
-    if (ctx->known_sel) {
+    if (known) {
         long share_sum = 0;
-        for (int b = 0; b < B && b < (int)ctx->known_sel->size(); ++b) {
-            const pb_fft_sel &e = (*ctx->known_sel)[(size_t)b];
+        for (int b = 0; b < B && b < (int)known->size(); ++b) {
+            const pb_fft_sel &e = (*known)[(size_t)b];
             if (!e.use_fft || e.poly == 0) continue;
             if (e.poly == 2) { share_sum += w128_per_of(g.ow, g.oh, e.hx, e.hy) * p.C; continue; }
-            const bool et = tall && e.poly == 1 && e.pad_[0] != 0;
-            const int tx = FT_N - 2 * e.hx, ty = (et ? 2 * FT_N : FT_N) - 2 * e.hy;
-            const long tiles_x = (g.ow + tx - 1) / tx;
-            const long nj = (et ? tiles_x : (tiles_x + 1) / 2) * ((g.oh + ty - 1) / ty);
-            share_sum += ((nj + 7) / 8 * p.C + 3) / 4;
+            share_sum += ((wfft_jobs_of(g, e, tall) + 7) / 8 * p.C + 3) / 4;
         }
         if (!share_sum) return PB_OK;
         groups = 8L * share_sum;

@@ -1185,7 +1185,7 @@ __global__ __launch_bounds__(NT) void blur_params_kernel(pb_blur_info *infos, co
                                                          float *khat_2, pb_fft_sel *fsel_2, const PolySpec ps_2, int set2_from) {
     // set2_from > 0: the workgroups blockIdx.y >= set2_from form a SECOND set of spectra + selections (khat_2, fsel_2) under the
     // spec ps_2 -- what a khat_kernel launch of its own between the estimation and the pass used to build (common.h:
-    // poly_want2).  They walk the same chain from the same maxima BESIDE the first set's workgroups (the chip is empty under
+    // spectra2).  They walk the same chain from the same maxima BESIDE the first set's workgroups (the chip is empty under
     // this kernel: 65 workgroups per image), so the chain to the first set's spectra is not a cycle longer.
     const bool second = set2_from > 0 && (int)blockIdx.y >= set2_from;
     const int slice_y = second ? (int)blockIdx.y - set2_from : (int)blockIdx.y;
@@ -1789,7 +1789,7 @@ bool pb_gradient_planes_half(pb_ctx *ctx, int H, int W) {
 }
 
 int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H, int W, const pb_options *opt,
-                     pb_blur_info *dev_info) {
+                     pb_blur_info *dev_info, const PolySpec &spec1, const PolySpec &ps2, int slot) {
     if (opt->q < 0.f || opt->q >= 0.5f) return pb_fail(ctx, PB_ERR_BADARG, "q must be in [0, 0.5)");
     const int ksize = pb_kernel_size(opt);
     if (!ksize) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "ker_size %d: sizes from 2 to %d are built", opt->ker_size, PB_KSIZE_MAX);
@@ -1873,19 +1873,19 @@ int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H
     if (rc) return rc;
     float *khat = nullptr;
     pb_fft_sel *fsel = nullptr;
+    const PassWant want{spec1, slot};
     if (ctx->fft_min_phases >= 0) {
-        rc = pb_khat_buffers(ctx, B, &khat, &fsel);
+        rc = pb_khat_buffers(ctx, B, want, &khat, &fsel);
         if (rc) return rc;
     }
     // (PolySpec.always under full support: the short chain to the spectra, the record beside it -- see the kernel)
-    const int lean = (khat && ctx->poly_want.always == 1 && opt->support == PB_SUPPORT_FULL && ctx->est_lean) ? 1 : 0;
-    // (the second set: where the call in progress has said it will need one -- api.hip sets poly_want2 around the estimation)
+    const int lean = (khat && spec1.always == 1 && opt->support == PB_SUPPORT_FULL && ctx->est_lean) ? 1 : 0;
+    // (the second set: where the call has said it will need one -- ps2, worked out by pb_polyblur_batch's plan of the iteration)
     float *khat2 = nullptr;
     pb_fft_sel *fsel2 = nullptr;
-    const PolySpec ps2 = ctx->poly_want2;
     ctx->spectra2.drop_if_overlaps(dev_info, dev_info + B);       // (these records are being rewritten)
     if (khat && (ps2.on != 0 || ps2.always != 0)) {
-        rc = pb_khat2_buffers(ctx, B, &khat2, &fsel2);
+        rc = pb_khat2_buffers(ctx, B, want, &khat2, &fsel2);
         if (rc) return rc;
     }
     ProfScope prof(ctx, PB_PROF_PARAMS);
@@ -1894,10 +1894,10 @@ int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H
     hipLaunchKernelGGL(blur_params_kernel, dim3(B, set1 + set2), dim3(NT), 0, ctx->stream, dev_info, mm, mags, wts, opt->n_angles,
                        opt->n_interpolated_angles, opt->c, opt->b, opt->support, opt->force_theta_deg, est_tiles, ksize,
                        (!(ksize & 1) && opt->boundary == PB_WRAP) ? 1 : 0, norm ? nullptr : part_q0, bpi_q0, mm, khat, fsel,
-                       ctx->fft_min_phases, ctx->poly_want, lean, khat2, fsel2, ps2, set2 ? set1 : 0);
+                       ctx->fft_min_phases, spec1, lean, khat2, fsel2, ps2, set2 ? set1 : 0);
     PB_LAUNCH_CHECK();
-    if (khat2) ctx->spectra2.claim(dev_info, B, ps2, ctx->sel_slot % PB_SEL_SLOTS, true);
-    if (khat) ctx->spectra.claim(dev_info, B, ctx->poly_want, ctx->sel_slot % PB_SEL_SLOTS, true);
+    if (khat2) ctx->spectra2.claim(dev_info, B, ps2, slot % PB_SEL_SLOTS, true);
+    if (khat) ctx->spectra.claim(dev_info, B, spec1, slot % PB_SEL_SLOTS, true);
     return PB_OK;
 }
 

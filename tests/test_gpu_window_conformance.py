@@ -7,8 +7,8 @@ Everything goes through the C ABI with host-built records of caller taps (Engine
 support, wrap boundary; tests/window_ref.py: dial_taps gives the taps of any halo pair, with a margin no fp32 evaluation of the
 halo rule can cross).  Six contexts: `pairs` (PB_POLY1=2, PB_POLY_TALL=0), `w128` (PB_POLY1=3, PB_POLY_TALL=0), `tall` (PB_POLY1=3,
 PB_POLY_TALL=2), `three` (PB_POLY1=0: three Horner steps), and `w128_merged` / `tall_merged` (as `w128` / `tall` with
-PB_POLY_ONE_LAUNCH=2: host-built records through conv_win_kernel with the exact grid, the known_sel branch of
-pb_launch_conv_win).  The cost model of csrc/khat.h decides which form an image takes in a context; the tests do not restate
+PB_POLY_ONE_LAUNCH=2: host-built records through conv_win_kernel with the exact grid, the branch of
+pb_launch_conv_win that is handed the records' selections).  The cost model of csrc/khat.h decides which form an image takes in a context; the tests do not restate
 it: they read the form from pb_body_selection (a 64 x 128 window reports as a 64 x 64 pair does: it is told by bits that differ
 from a 64 x 64 run of the same image, or by a halo pair that leaves a 64 x 64 window no admissible tile), check whatever ran,
 and the coverage tests assert that every halo value and every joint corner each form admits by csrc/common.h's constants was
