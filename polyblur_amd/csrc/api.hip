@@ -108,10 +108,27 @@ static void pb_read_knobs(pb_ctx *ctx) {
 #ifdef PB_EXPERIMENTAL
     geti("PB_STRIP", ctx->strip_mode);
 #endif
-    geti("PB_EST_GRAY_ROWS", ctx->est_gray_rows); geti("PB_EST_LEAN", ctx->est_lean); geti("PB_DT_ROWS_REG", ctx->dt_rows_reg); geti("PB_DT_COLS_STRIP", ctx->dt_cols_strip); geti("PB_DT_COLS_COOP", ctx->dt_cols_coop);
-    geti("PB_FFT_EXT_RADIX", ctx->fft_ext_radix); geti("PB_FFT_FIRST", ctx->fft_first); geti("PB_FFT_FIRST_ROWS", ctx->fft_first_rows); geti("PB_COLS_FIXED", ctx->cols_fixed); geti("PB_ROWS_FIXED", ctx->rows_fixed);
+    geti("PB_EST_GRAY_ROWS", ctx->line.est_gray_rows); geti("PB_EST_LEAN", ctx->est_lean); geti("PB_DT_ROWS_REG", ctx->dt_rows_reg); geti("PB_DT_COLS_STRIP", ctx->dt_cols_strip); geti("PB_DT_COLS_COOP", ctx->dt_cols_coop);
+    geti("PB_FFT_EXT_RADIX", ctx->line.fft_ext_radix); geti("PB_FFT_FIRST", ctx->line.fft_first); geti("PB_FFT_FIRST_ROWS", ctx->line.fft_first_rows); geti("PB_COLS_FIXED", ctx->line.cols_fixed); geti("PB_ROWS_FIXED", ctx->line.rows_fixed);
     geti("PB_POLY1", ctx->poly_mode); geti("PB_POLY_TALL", ctx->poly_tall); geti("PB_POLY_ONE_LAUNCH", ctx->poly_one_launch);
     geti("PB_POLY_ALWAYS", ctx->poly_always); geti("PB_POLY_PADDED", ctx->poly_padded); geti("PB_TAPER_RING", ctx->taper_ring); geti("PB_ZERO_RING", ctx->zero_ring); getl("PB_ZERO_RING_MIN_PAIRS", ctx->zero_ring_min_pairs);
+}
+
+// What the line transforms of the estimation would run for one launch (line_choice.h), under the knobs of the environment as
+// pb_create reads them; host only, no device needed.  axis 0: rows of n samples, `other` of them per plane; 1: columns of n
+// samples, `other` of them; use = LineUse's seven fields in order.  out (37 ints): kind, taken, threads, lognb, tiles, lds,
+// max_radix, sat, half_ok, ext, first, bluestein_m, nstage, the radices.  axis 2: out[0] = pb_gradient_planes_half for n x other.
+extern "C" int pb_debug_line_choice(int axis, int n, int other, int P, const int *use, int *out) {
+    if (axis < 0 || axis > 2 || n < 2 || other < 2 || P < 1 || !use || !out) return PB_ERR_BADARG;
+    pb_ctx ctx;
+    pb_read_knobs(&ctx);
+    if (axis == 2) { out[0] = pb_gradient_planes_half(&ctx, n, other) ? 1 : 0; return PB_OK; }
+    const LineUse u{use[0], use[1], use[2], use[3], use[4], use[5], use[6]};
+    const LineChoice c = axis == 0 ? choose_rows(ctx.host_plans, ctx.line, n, other, P, u) : choose_cols(ctx.host_plans, ctx.line, n, other, P, u);
+    const int head[13] = {c.kind, c.taken, c.threads, c.lognb, c.tiles, c.lds, c.max_radix, c.sat, c.half_ok, c.ext, c.first, c.plan.bluestein_m, c.plan.nstage};
+    std::copy(head, head + 13, out);
+    std::copy(c.plan.radix, c.plan.radix + 24, out + 13);
+    return PB_OK;
 }
 
 extern "C" {

@@ -10,16 +10,13 @@
 #include <vector>
 
 #include "../../include/polyblur_hip.h"
+#include "line_choice.h"
 
 
 // ------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------
-struct FftPlan {
-    int n = 0;
-    int nstage = 0;
-    int radix[24];
-    int bluestein_m = 0;          // 0: direct mixed-radix; else the power-of-two length used
+struct FftPlan : HostPlan {      // (line_choice.h has the host half: n, the radices, the Bluestein core)
     float2 *tw = nullptr;         // W_n^m (or W_m^m for bluestein), m = 0..n-1
     float *drev = nullptr;        // derivative multiplier in digit-reversed order, / n
     // bluestein extras
@@ -118,7 +115,8 @@ struct pb_ctx {
     hipStream_t stream = nullptr;
     std::string err;
     std::map<std::string, ScratchBuf> scratch;
-    std::map<int, FftPlan> plans;
+    std::map<int, FftPlan> plans;   // the plans whose tables are on the device (pb_get_plan), by plan_key
+    HostPlans host_plans;           // ... and the host halves the line transforms' choice has looked at (line_choice.h)
     float *interp_w = nullptr;     // (n_interp x (n_angles+1)) Keys weights
     int interp_na = 0, interp_ni = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_switch = nullptr;
@@ -177,13 +175,8 @@ struct pb_ctx {
     int dt_cols_coop = 1;                // env PB_DT_COLS_COOP: 0 = never the few-columns form of the column pass (dt_cols_coop_kernel), 2 = always where it applies
     int dt_rows_reg = 1;                 // env PB_DT_ROWS_REG: 0 = the domain-transform row pass always through global memory (dt_rows_fused_kernel), 2 = registers, one wave per row always, 3 = a row over four waves always (dt_rows_regw_kernel)
     int poly_always = 1;                 // env PB_POLY_ALWAYS: 0 = never PolySpec.always (every polynomial issues all the launches its records might need)
-    int est_gray_rows = 1;               // env PB_EST_GRAY_ROWS: 1 = gray + range + row transform in one launch where measured faster (fp32 planes, lines of up to 4096 samples), 2 = for any line held in LDS, 0 = never
-    int fft_ext_radix = 1;               // env PB_FFT_EXT_RADIX: 0 = greedy plans only (radices up to 16)
-    int fft_first_rows = -1;             // env PB_FFT_FIRST_ROWS: the same for the row transforms (rows_plan)
-    int fft_first = -1;                  // env PB_FFT_FIRST: the radix of the column transform's first / last stage where the plan holds it; 0 = the plan's own order; -1 = chosen by trips (launch_cols)
+    LineKnobs line;                      // env PB_EST_GRAY_ROWS, PB_FFT_EXT_RADIX, PB_FFT_FIRST, PB_FFT_FIRST_ROWS, PB_COLS_FIXED, PB_ROWS_FIXED: what the line transforms' choice reads (line_choice.h)
     // tuning / comparison knobs of single kernels, read once in pb_create (the table of every knob: api.hip, pb_read_knobs)
-    int cols_fixed = 1;                  // env PB_COLS_FIXED: 0 = the column transform always by the run-time-plan kernel (grad_cols_kernel), also where lines_fixed.hip holds the plan
-    int rows_fixed = 1;                  // env PB_ROWS_FIXED: the same for the row transforms (gray_rows_kernel / grad_rows_kernel)
     size_t phase_budget = 0;             // pb_set_phase_budget: bytes of complex scratch one group of plane pairs of the pure-phase polynomial may take (conv_phase.hip); 0 = 256 MiB.  One pair is always allowed
     int poly_one_launch = 1;             // env PB_POLY_ONE_LAUNCH: 0 = the window pass of a PolySpec.always polynomial as two launches (conv_w128.hip, conv_wfft.hip) instead of one (conv_win.hip); 2 = host-built records take the one launch too (tools/one_launch_timing.py)
     int poly_tall = 1;                   // env PB_POLY_TALL: one-pass images on windows 64 wide and 128 tall -- 0 = never, 1 = where the cost model of khat.h prices them lowest, 2 = every image the form admits
@@ -214,7 +207,7 @@ struct ProfScope {
     }
 };
 void *pb_scratch(pb_ctx *ctx, const char *name, size_t bytes);   // nullptr on failure (error set)
-const FftPlan *pb_get_plan(pb_ctx *ctx, int n, bool ext_radices = false, int first = 0);   // ext_radices: the caller's kernel holds radices 18 / 20 / 24; first: the radix (one of the plan's) of the stages that talk to global memory, 0 = the plan's own order
+const FftPlan *pb_get_plan(pb_ctx *ctx, int n, bool ext_radices = false, int first = 0);   // host_plan(n, ext_radices, first) with its tables on the device
 const float *pb_get_interp_weights(pb_ctx *ctx, int n_angles, int n_interp);
 
 #define PB_HIP(call)                                                                          \

@@ -58,51 +58,6 @@ constexpr int NT = 256;
 // ------------------------------------------------------------------------------------
 // FFT plans (host)
 // ------------------------------------------------------------------------------------
-static void factorize(int n, std::vector<int> &radix, int &rest, bool ext_ok = false) {
-    // greedy: the largest in-register radix that divides what is left (fewer LDS passes and barriers)
-    static const int pref[] = {16, 15, 12, 10, 9, 8, 6, 5, 4, 7, 3, 2};
-    radix.clear();
-    const int n0 = n;
-    bool found = true;
-    while (n > 1 && found) {
-        found = false;
-        for (int r : pref)
-            if (n % r == 0) { radix.push_back(r); n /= r; found = true; break; }
-    }
-    rest = n;
-    // Lines held in LDS: where radices 18 / 20 / 24 save a stage over the greedy plan (4320 = 16 x 15 x 9 x 2 -> 18 x 16 x 15,
-    // 7680 = 16 x 16 x 15 x 2 -> 24 x 20 x 16: two LDS round trips and barriers fewer per line), the plan with the fewest
-    // stages and, among those, the smallest sum of radices; every other length keeps its greedy plan.
-    if (!ext_ok || rest != 1 || (long)n0 * 8 > 160 * 1024 || radix.size() < 3) return;
-    static const int ext[] = {24, 20, 18, 16, 15, 12, 10, 9, 8, 6, 5, 4, 7, 3, 2};
-    std::vector<int> best, cur;
-    int best_sum = 0;
-    const size_t limit = radix.size() - 1;                // only plans with fewer stages are of interest
-    std::function<void(int, int, int)> dfs = [&](int left, int max_r, int sum) {
-        if (left == 1) {
-            if (best.empty() || cur.size() < best.size() || (cur.size() == best.size() && sum < best_sum)) { best = cur; best_sum = sum; }
-            return;
-        }
-        if (cur.size() >= limit || (!best.empty() && cur.size() >= best.size())) return;
-        for (int r : ext) {
-            if (r > max_r || left % r) continue;
-            cur.push_back(r);
-            dfs(left / r, r, sum + r);
-            cur.pop_back();
-        }
-    };
-    dfs(n0, 24, 0);
-    if (best.empty() || best.size() >= radix.size()) return;
-    // order: the first radix is the one of the stages that talk to global memory (and, in the column kernel, carry the
-    // epilogue's prefetched operands): the largest one up to 16, as in the greedy plans; the rest ascending, so that the
-    // widest butterfly is the innermost stage, which has no twiddles to hold
-    std::sort(best.begin(), best.end());
-    int first = -1;
-    for (int i = (int)best.size() - 1; i >= 0; --i) if (best[i] <= 16) { first = i; break; }
-    if (first > 0) std::rotate(best.begin(), best.begin() + first, best.begin() + first + 1);
-    radix = best;
-}
-
 // frequency index held at position p after the DIF stages
 static int digit_reversed_freq(int p, int n, const std::vector<int> &radix) {
     int k = 0, weight = 1, stride = n;
@@ -149,30 +104,15 @@ extern "C" int pb_fft_length_supported(int n) {
 }
 
 const FftPlan *pb_get_plan(pb_ctx *ctx, int n, bool ext_radices, int first) {
-    // (two plans per length: the kernel variants without the radices above 16 take the greedy one; and one per first radix asked for)
-    const int key = (ext_radices ? -1 : 1) * (n + (first << 17));
+    const int key = plan_key(n, ext_radices, first);
     auto it = ctx->plans.find(key);
     if (it != ctx->plans.end()) return &it->second;
     FftPlan pl;
-    pl.n = n;
-    std::vector<int> radix;
-    int rest = 1;
-    factorize(n, radix, rest, ext_radices && ctx->fft_ext_radix != 0);
+    static_cast<HostPlan &>(pl) = host_plan(ctx->host_plans, ctx->line, n, ext_radices, first);
+    if (!pl.nstage) { pb_fail(ctx, PB_ERR_UNSUPPORTED, "fft length %d: too many stages", n); return nullptr; }
+    const std::vector<int> radix(pl.radix, pl.radix + pl.nstage);
     const double two_pi = 6.283185307179586476925286766559;
-    int core = n;
-    if (rest != 1) {               // Bluestein with a power-of-two core
-        core = 1;
-        while (core < 2 * n - 1) core *= 2;
-        pl.bluestein_m = core;
-        factorize(core, radix, rest);
-    }
-    if (first > 0 && !pl.bluestein_m) {
-        auto it = std::find(radix.begin(), radix.end(), first);
-        if (it != radix.end()) std::rotate(radix.begin(), it, it + 1);
-    }
-    if ((int)radix.size() > 24) { pb_fail(ctx, PB_ERR_UNSUPPORTED, "fft length %d: too many stages", n); return nullptr; }
-    pl.nstage = (int)radix.size();
-    for (int i = 0; i < pl.nstage; ++i) pl.radix[i] = radix[i];
+    const int core = pl.bluestein_m ? pl.bluestein_m : n;
     std::vector<float2> tw(core);
     for (int m = 0; m < core; ++m) {
         const double a = -two_pi * m / core;
@@ -1445,51 +1385,10 @@ __global__ __launch_bounds__(NT) void make_kernels_kernel(pb_blur_info *infos, i
     finish_record(infos + blockIdx.x, support, from_taps != 0, red, ksize);
 }
 
-bool plan_ext(const FftPlan *pl) {                    // a plan holding radices above 16: only some kernel variants run it
-    for (int i = 0; i < pl->nstage; ++i) if (pl->radix[i] > 16) return true;
-    return false;
-}
-
-size_t fft_lds_bytes(const FftPlan *pl, int nb) {
-    const size_t n = pl->bluestein_m ? pl->bluestein_m : pl->n;
-    return n * nb * sizeof(float2);
-}
-
-constexpr size_t kMaxLds = 160 * 1024;
-
 template <typename K> int allow_lds(pb_ctx *ctx, K kernel, size_t bytes) {
     if (bytes > 48 * 1024)
         PB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return PB_OK;
-}
-
-// choose how many complex lines a column workgroup transforms together, and with how many threads.  Base rule: the
-// widest tile whose lines fit 80 KB of LDS (two 256-thread workgroups per CU).  For the estimation's default kernel
-// (maxima of 7 directions, fused plan) one 512-thread workgroup with a tile twice as wide is 7 % faster when it fits:
-// the same waves per CU, but half as many 128-byte lines requested per useful byte of the column segments
-// (measured, 4K: 73.7 -> 68.5 us; 8 x 1080p: 132 -> 122 us; 512 threads on the narrow tile: 95 us; one 700x500 image,
-// whose 44 narrow tiles already leave most CUs idle: 31.7 -> 35.9 us, hence the workgroup-count condition).
-int pick_lognb(pb_ctx *ctx, const FftPlan *pl, int W, int P, bool wide_ok, int *threads, bool fixed_maxima = false) {
-    if (fft_lds_bytes(pl, 1) > kMaxLds) {          // lines through global memory (grad_cols_long_kernel): 8-column tiles
-        int lognb = 2;
-        while (lognb > 0 && (2 << (lognb - 1)) >= W * 2) --lognb;
-        if (threads) *threads = LONG_NT;
-        return lognb;
-    }
-    int lognb = 3;
-    while (lognb > 0 && fft_lds_bytes(pl, 1 << lognb) > 80 * 1024) --lognb;
-    while (lognb > 0 && (2 << (lognb - 1)) >= W * 2) --lognb;
-    int nt = NT;
-    if (wide_ok && !pl->bluestein_m && pl->nstage >= 2 &&
-        fft_lds_bytes(pl, 2 << lognb) <= 140 * 1024 && (long)P * (W / (4 << lognb)) >= 200 &&   // still fills the chip
-        // (1080-point lines through lines_fixed.hip: two 512-thread workgroups per CU on 16-column tiles -- 69 KB each, one's
-        // requests under the other's stages -- beat one 1024-thread workgroup on a 32-column tile: 32 x 1080p 174 against 198 us)
-        !(fixed_maxima && pl->n == 1080 && (W % 16) == 0)) {
-        ++lognb;
-        nt = 512;
-    }
-    if (threads) *threads = nt;
-    return lognb;
 }
 
 // Workgroups of a through-memory transform: one per work item up to what keeps the slots within 256 MB (at least 64)
@@ -1499,61 +1398,33 @@ long long_grid(long items, size_t slot_bytes) {
     return std::max(1L, std::min(items, g));
 }
 
-// Rows: a workgroup's transform is a chain of dependent stages, so the kernel is as fast as the number of chains in
-// flight.  Lines of up to 4096 samples (32 KB of LDS per two rows) fit five workgroups per CU; with many more
-// workgroups than that they run 128 threads.  Longer lines are limited by LDS to two or three workgroups per CU and
-// keep 256 threads (measured at 7680: 241 us per 8K image against 339 us with 128).
-// How many threads the row kernels run a line pair with (launch_rows and launch_gray_rows; the comments there).
-static int rows_threads(pb_ctx *ctx, const FftPlan *pl, size_t lds, long blocks) {
-    const bool one_round = blocks <= 256L * 5;
-    if (!plan_ext(pl) && lds <= 32 * 1024 && !one_round) return 128;
-    if (plan_ext(pl) || lds > 40 * 1024) return 512;
-    return 256;
-}
+// The launchers below run what line_choice.h chose for the launch (plan, tile, threads, kernel: choose_rows / choose_cols have
+// the rules and the measurements behind them); they decide nothing.
+static_assert(LONG_NT == kLineLongThreads, "the through-memory kernels' workgroup");
 
-// Which of a plan's radices its first and last stage should take -- the two that talk to global memory: the smallest one
-// (up to 16) that is at least `always_from`, or at least `min_r` with n / r <= max_items butterflies per line; 0 = the
-// plan's own first radix.  A function of the plan and the line length ALONE: the order of the stages decides the roundings,
-// and an image gets the same bits alone and in a batch (tests/test_gpu_fullsize.py, test_gpu_round5_forms.py).
-static int first_radix_for(const FftPlan *pl, int n, int max_items, int always_from, int min_r) {
-    if (pl->bluestein_m || pl->nstage < 2) return 0;
-    int first = pl->radix[0];
-    for (int i = 1; i < pl->nstage; ++i) {
-        const int r = pl->radix[i];
-        if (r <= 16 && r < first && (r >= always_from || (r >= min_r && n / r <= max_items))) first = r;
-    }
-    return first == pl->radix[0] ? 0 : first;
-}
+LineUse planes_use(int out_dtype, bool normalize) { LineUse u; u.out_dtype = out_dtype; u.normalize = normalize; return u; }
 
-// The row transforms' plan: of its radices (2 .. 16) the smallest whose n / r butterflies are one trip for 256 threads goes
-// first.  Fewer loads and a smaller butterfly between a thread's loads and its LDS writes, every thread busy: 1920 = 16 x
-// 15 x 8 is 120 butterflies of radix 16 or 240 of radix 8.  Measured per launch (one image, 256 threads): 1080p 24.2 ->
-// 21.0 us (8 first), 1280-sample rows 23.0 -> 19.5 (5), 700-sample rows 16.3 -> 15.1 (7), 1024 21.0 -> 16.0 (4), 720 22.6
-// -> 15.9 (3), 512 18.6 -> 12.4 (2: 256 threads loading instead of 32); batches on 128 threads: 16 x 720-sample rows 126 ->
-// 93 us, 8 x 1024 57 -> 50, 32 x 1080p -- where radix 8 is a second trip -- 304 -> 307 (15 first: 289).  launch_cols has
-// the column transform's rule.
-static const FftPlan *rows_plan(pb_ctx *ctx, int n) {
-    const FftPlan *pl = pb_get_plan(ctx, n, true);       // (the 512-thread variant holds the radices above 16)
-    if (!pl || ctx->fft_first_rows == 0 || fft_lds_bytes(pl, 1) > kMaxLds) return pl;
-    const int first = ctx->fft_first_rows > 0 ? ctx->fft_first_rows : first_radix_for(pl, n, 256, 17, 2);
-    return first > 0 && first != pl->radix[0] ? pb_get_plan(ctx, n, true, first) : pl;
-}
-
-int launch_rows(pb_ctx *ctx, const float *planes, float *gx, int P, int H, int W, bool normalize,
-                const unsigned *mm, int planes_per_image, int gx_dtype = PB_F32) {      // (gx_dtype PB_F16: __half planes behind `gx`, fixed-plan kernels only)
-    const long blocks = (long)P * ((H + 1) / 2);
-    const FftPlan *pl = rows_plan(ctx, W);
+// (gx_dtype PB_F16: __half planes behind `gx`, out of the compiled-plan kernels only)
+int launch_rows(pb_ctx *ctx, const LineChoice &c, const float *planes, void *gx, int P, int H, int W, bool normalize,
+                const unsigned *mm, int planes_per_image, int gx_dtype = PB_F32) {
+    if (gx_dtype != PB_F32 && !c.half_ok) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "row transform: fp16 planes out of the compiled-plan kernels only");
+    const long blocks = (long)P * c.tiles;
+    const size_t lds = (size_t)c.lds;
+    const FftPlan *pl = pb_get_plan(ctx, W, c.ext != 0, c.first);
     if (!pl) return PB_ERR_NOMEM;
-    const size_t lds = fft_lds_bytes(pl, 1);
+    if (c.kind == PB_LINE_COMPILED) {
+        ProfScope prof(ctx, PB_PROF_GRAD_ROWS);
+        return pb_launch_rows_fixed(ctx, c, planes, 0, nullptr, gx, nullptr, P, H, pl, gx_dtype);
+    }
     const pbfft::DevPlan dp = dev_plan(pl);
-    if (lds > kMaxLds) {                            // the line buffer in global memory, one slot per workgroup
-        if (gx_dtype != PB_F32) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "row transform: fp16 planes out of the compiled-plan kernels only");
+    float *gxf = static_cast<float *>(gx);
+    if (c.kind == PB_LINE_MEMORY) {                 // the line buffer in global memory, one slot per workgroup
         if (!pb_fft_length_supported(W)) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "image width %d: lines of up to %d samples are supported", W, kMaxLineLength);
         const long grid = long_grid(blocks, lds);
         float2 *slots = static_cast<float2 *>(pb_scratch(ctx, "fft.long", (size_t)grid * lds));
         if (!slots) return PB_ERR_NOMEM;
         ProfScope prof(ctx, PB_PROF_GRAD_ROWS);
-        hipLaunchKernelGGL(grad_rows_long_kernel, dim3((unsigned)grid), dim3(LONG_NT), 0, ctx->stream, planes, gx, H, W,
+        hipLaunchKernelGGL(grad_rows_long_kernel, dim3((unsigned)grid), dim3(LONG_NT), 0, ctx->stream, planes, gxf, H, W,
                            normalize ? 1 : 0, mm, planes_per_image, dp, slots, blocks);
         PB_LAUNCH_CHECK();
         return PB_OK;
@@ -1565,51 +1436,32 @@ int launch_rows(pb_ctx *ctx, const float *planes, float *gx, int P, int H, int W
         int rc = allow_lds(ctx, grad_rows_kernel<NTH, FUSED>, lds);                                              \
         if (rc) return rc;                                                                                       \
         hipLaunchKernelGGL((grad_rows_kernel<NTH, FUSED>), dim3((unsigned)blocks), dim3(NTH), lds, ctx->stream,  \
-                           planes, gx, H, W, normalize ? 1 : 0, mm, planes_per_image, dp);                       \
+                           planes, gxf, H, W, normalize ? 1 : 0, mm, planes_per_image, dp);                      \
     } while (0)
-    // A grid that fits the chip in ONE round of five workgroups per CU (a single 4K image: 1080) is a race of dependent
-    // chains, and 256 threads -- one butterfly per thread and stage, held to 96 registers so that five such workgroups
-    // still fit a CU -- shorten every chain: 41.0 -> 33.4 us at 4K, 17.4 -> 15.8 us at 700 x 500.  Larger grids are
-    // throughput-bound and keep 128 threads (8 x 1080p: 63.7 us against 70.0 with 256).
-    const int nth = rows_threads(ctx, pl, lds, blocks);
-    // (line lengths whose plan is compiled in -- lines_fixed.hip: 3840, 1920, 7680 --: the same butterflies in a one-plan kernel
-    // on a padded LDS line; PB_ROWS_FIXED=0: this file's kernel, the tests' reference)
-    if (fused && !normalize && ctx->rows_fixed) {
-        const int rcf = pb_launch_rows_fixed(ctx, planes, 0, nullptr, gx, nullptr, P, H, W, nth, pl, gx_dtype);
-        if (rcf != PB_ERR_UNSUPPORTED) return rcf;
-    }
-    if (gx_dtype != PB_F32) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "row transform: fp16 planes out of the compiled-plan kernels only");
     if (!fused) PB_ROWS(256, false);
-    else if (nth == 128) PB_ROWS(128, true);
-    else if (nth == 512) PB_ROWS(512, true);
+    else if (c.threads == 128) PB_ROWS(128, true);
+    else if (c.threads == 512) PB_ROWS(512, true);
     else PB_ROWS(256, true);
 #undef PB_ROWS
     PB_LAUNCH_CHECK();
     return PB_OK;
 }
 
-// gray + range partials + row transform in one launch (gray_rows_kernel); PB_ERR_UNSUPPORTED where the lines do not take the
-// fused transform (the caller then runs the gray pass and launch_rows).  *partials = partials per image.
-int launch_gray_rows(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H, int W, float *gray, float *gx, float2 **part,
-                     int *partials) {
-    const int on = ctx->est_gray_rows;
-    if (!on) return PB_ERR_UNSUPPORTED;
-    const FftPlan *pl = rows_plan(ctx, W);
+// gray + range partials + row transform in one launch (gray_rows_kernel), where the choice takes it (c.taken; otherwise the
+// caller runs the gray pass and launch_rows).  *partials = partials per image.
+int launch_gray_rows(pb_ctx *ctx, const LineChoice &c, const void *in, int B, int C, int H, int W, float *gray, float *gx,
+                     float2 **part, int *partials) {
+    if (!c.taken) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "gray + row transform in one launch: not taken for %d-sample lines", W);
+    const long blocks = (long)B * c.tiles;
+    const size_t lds = (size_t)c.lds;
+    const FftPlan *pl = pb_get_plan(ctx, W, c.ext != 0, c.first);
     if (!pl) return PB_ERR_NOMEM;
-    const size_t lds = fft_lds_bytes(pl, 1);
-    if (lds > kMaxLds || pl->bluestein_m || pl->nstage < 2) return PB_ERR_UNSUPPORTED;
-    // Measured (same box, PB_EST_GRAY_ROWS=0/1): 4K fp32 0.820 -> 0.811 ms per call, 32 x 1080p fp32 7.11 -> 7.00 ms; but 8K
-    // lines (two workgroups per CU: six load streams with nothing to hide them behind) 4.22 -> 4.33 ms, and fp16 / 8-bit
-    // planes (2- and 1-byte loads where the gray pass reads 8 and 4 bytes per lane) 35.0 -> 35.4 ms for 64 x 1080p fp16: the
-    // fused launch is built for fp32 planes and taken for lines of up to 4096 samples (PB_EST_GRAY_ROWS=2: any length).
-    if (dtype != PB_F32 || (on < 2 && lds > 32 * 1024)) return PB_ERR_UNSUPPORTED;
-    const int pairs = (H + 1) / 2;
-    const long blocks = (long)B * pairs;
-    if (blocks > 0x7fffffffL) return PB_ERR_UNSUPPORTED;
     float2 *pt = static_cast<float2 *>(pb_scratch(ctx, "est.part", sizeof(float2) * (size_t)blocks));
     if (!pt) return PB_ERR_NOMEM;
-    const pbfft::DevPlan dp = dev_plan(pl);
+    *part = pt; *partials = c.tiles;
     ProfScope prof(ctx, PB_PROF_GRAD_ROWS);
+    if (c.kind == PB_LINE_COMPILED) return pb_launch_rows_fixed(ctx, c, static_cast<const float *>(in), C, gray, gx, pt, B, H, pl, PB_F32);
+    const pbfft::DevPlan dp = dev_plan(pl);
 #define PB_GROWS(T, CC, NTH)                                                                                       \
     do {                                                                                                           \
         int rc = allow_lds(ctx, gray_rows_kernel<T, CC, NTH>, lds);                                                \
@@ -1619,154 +1471,71 @@ int launch_gray_rows(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H
     } while (0)
 #define PB_GROWS_C(T, NTH) do { if (C == 3) PB_GROWS(T, 3, NTH); else PB_GROWS(T, 0, NTH); } while (0)
 #define PB_GROWS_T(NTH) PB_GROWS_C(float, NTH)
-    // (as launch_rows; lines above 40 KB of LDS -- 8K rows -- leave room for two or three workgroups per CU: 512 threads each
-    // keep the CU's SIMDs supplied)
-    const int nth = rows_threads(ctx, pl, lds, blocks);
-    if (ctx->rows_fixed && (C == 3 || C == 1)) {                       // (as launch_rows)
-        const int rcf = pb_launch_rows_fixed(ctx, static_cast<const float *>(in), C, gray, gx, pt, B, H, W, nth, pl);
-        if (rcf != PB_ERR_UNSUPPORTED) {
-            if (rcf == PB_OK) { *part = pt; *partials = pairs; }
-            return rcf;
-        }
-    }
-    if (nth == 128) PB_GROWS_T(128);
-    else if (nth == 512) PB_GROWS_T(512);
+    if (c.threads == 128) PB_GROWS_T(128);
+    else if (c.threads == 512) PB_GROWS_T(512);
     else PB_GROWS_T(256);
 #undef PB_GROWS_T
 #undef PB_GROWS_C
 #undef PB_GROWS
     PB_LAUNCH_CHECK();
-    *part = pt; *partials = pairs;
     return PB_OK;
 }
 
-int launch_cols(pb_ctx *ctx, const float *planes, const float *gx, float *gy, int P, int H, int W, int mode,
+// mode 0: gy = the y derivative of the planes (gy_dtype PB_F16: as launch_rows); 1: the directional maxima into mags
+int launch_cols(pb_ctx *ctx, const LineChoice &c, const float *planes, const float *gx, void *gy, int P, int H, int W, int mode,
                 bool normalize, const unsigned *mm, int planes_per_image, unsigned *mags, int n_angles,
-                int discard_sat, int gy_dtype = PB_F32) {                           // (gy_dtype PB_F16: as launch_rows)
-    // (the 1024-thread variants of the gy-writing and the 7-direction kernels exist with the radices above 16)
-    const bool ext_variant = mode == 0 || (mode == 1 && n_angles == 6);
-    const FftPlan *pl = pb_get_plan(ctx, H, ext_variant);
-    if (!pl) return PB_ERR_NOMEM;
-    const bool ext = plan_ext(pl);
-    int nt = NT;
-    const int lognb = pick_lognb(ctx, pl, W, P, (mode == 1 && n_angles == 6) || mode == 0, &nt, mode == 1 && n_angles == 6 && !normalize && ctx->cols_fixed);
-    const size_t lds = fft_lds_bytes(pl, 1 << lognb);
-    const bool through_memory = fft_lds_bytes(pl, 1) > kMaxLds;
-    // Which of the plan's radices the first and the last stage take -- the two that talk to global memory, the last one with
-    // the epilogue's operands (gx, the gray sample) prefetched for every output of its butterfly and the directional maxima
-    // folded behind it.  The SMALLEST: fewer values per thread between the loads and the butterfly, fewer operands held for
-    // the epilogue (the 1024-thread variants have 128 registers per thread), and trips over the workgroup's threads that
-    // are full -- 2160 = 16 x 15 x 9 in tiles of 16 columns is 1080 butterflies of radix 16 for 1024 threads, a second
-    // trip for 56 of them, or 1920 of radix 9.  Measured per launch, greedy order -> smallest first: 4K 48.5 -> 43.3 us
-    // (9; 15 first: 45.2), 1080p 40.7 -> 32.0 (6; 12 first: 36.5), 1440p 50.5 -> 45.3 (6), 1920 x 1200 41.1 -> 35.2 (5),
-    // 1920 x 1280 40.0 -> 35.9 (5), 720p 28.3 -> 26.9 (3), 500 x 700 31.1 -> 28.4 (7), 2048^2 33.7 -> 33.1 (8);
-    // 32 x 1080p 394 -> 323 us.  Radices below 5 only for lines of up to 256 of their butterflies (every trip is a round
-    // trip to memory): 512 x 512 24.6 -> 20.8 us with 2 first, 3000-sample columns -- twelve trips of radix 2 -- no different.
-    // A function of the line length alone, as rows_plan's.
-    if (!through_memory && ctx->fft_first != 0) {
-        const int first = ctx->fft_first > 0 ? ctx->fft_first : first_radix_for(pl, H, 256, 5, 2);
-        if (first > 0 && first != pl->radix[0]) {
-            pl = pb_get_plan(ctx, H, ext_variant, first);
-            if (!pl) return PB_ERR_NOMEM;
-        }
-    }
-    if (through_memory && !pb_fft_length_supported(H))
+                int discard_sat, int gy_dtype = PB_F32) {
+    if (gy_dtype != PB_F32 && !c.half_ok) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "column transform: fp16 planes out of the compiled-plan kernels only");
+    if (c.kind == PB_LINE_MEMORY && !pb_fft_length_supported(H))
         return pb_fail(ctx, PB_ERR_UNSUPPORTED, "image height %d: lines of up to %d samples are supported", H, kMaxLineLength);
-    const int tc = 2 << lognb;
-    const long blocks = (long)P * ((W + tc - 1) / tc);
+    const FftPlan *pl = pb_get_plan(ctx, H, c.ext != 0, c.first);
+    if (!pl) return PB_ERR_NOMEM;
+    const int lognb = c.lognb;
+    const size_t lds = (size_t)c.lds;
+    const long blocks = (long)P * c.tiles;
     if (blocks > 0x7fffffffL) return pb_fail(ctx, PB_ERR_BADARG, "column transform: bad grid");
+    if (c.kind == PB_LINE_COMPILED) {
+        ProfScope prof(ctx, PB_PROF_GRAD_COLS);
+        return pb_launch_cols_fixed(ctx, c, planes, gx, P, W, mags, n_angles, pl, mode == 0 ? gy : nullptr, gy_dtype);
+    }
     const pbfft::DevPlan dp = dev_plan(pl);
     const float thr = 0.99f;
+    float *gyf = static_cast<float *>(gy);
     PbAngleTable ang;
     pb_angle_table(n_angles, ang.cs, ang.sn, PB_MAX_ANGLES);
-    if (through_memory) {                           // as launch_rows: a slot of 2 << lognb columns per workgroup
+    if (c.kind == PB_LINE_MEMORY) {                 // as launch_rows: a slot of 2 << lognb columns per workgroup
         const long grid = long_grid(blocks, lds);
         float2 *slots = static_cast<float2 *>(pb_scratch(ctx, "fft.long", (size_t)grid * lds));
         if (!slots) return PB_ERR_NOMEM;
         ProfScope prof(ctx, PB_PROF_GRAD_COLS);
         if (mode == 0)
-            hipLaunchKernelGGL(grad_cols_long_kernel<0>, dim3((unsigned)grid), dim3(LONG_NT), 0, ctx->stream, planes, gx, gy, H, W, lognb,
+            hipLaunchKernelGGL(grad_cols_long_kernel<0>, dim3((unsigned)grid), dim3(LONG_NT), 0, ctx->stream, planes, gx, gyf, H, W, lognb,
                                normalize ? 1 : 0, mm, planes_per_image, mags, n_angles, discard_sat, thr, (int)blocks, dp, ang, slots);
         else
-            hipLaunchKernelGGL(grad_cols_long_kernel<1>, dim3((unsigned)grid), dim3(LONG_NT), 0, ctx->stream, planes, gx, gy, H, W, lognb,
+            hipLaunchKernelGGL(grad_cols_long_kernel<1>, dim3((unsigned)grid), dim3(LONG_NT), 0, ctx->stream, planes, gx, gyf, H, W, lognb,
                                normalize ? 1 : 0, mm, planes_per_image, mags, n_angles, discard_sat, thr, (int)blocks, dp, ang, slots);
         PB_LAUNCH_CHECK();
         return PB_OK;
     }
     ProfScope prof(ctx, PB_PROF_GRAD_COLS);
-    // the line lengths whose plan is compiled in (lines_fixed.hip: 2160, 1080, 4320, on every tile width pick_lognb gives them):
-    // the same arithmetic in a kernel that holds one plan -- bit-identical maxima (PB_COLS_FIXED=0: the run-time-plan kernel,
-    // the tests' reference)
-    if (mode == 1 && !normalize && ctx->cols_fixed) {
-        const int rcf = pb_launch_cols_fixed(ctx, planes, gx, P, H, W, lognb, mags, n_angles, discard_sat, pl);
-        if (rcf != PB_ERR_UNSUPPORTED) return rcf;
-    }
-    if (mode == 0 && !normalize && ctx->cols_fixed && !through_memory) {
-        const int rcf = pb_launch_cols_fixed(ctx, planes, nullptr, P, H, W, lognb, nullptr, 0, 0, pl, gy, gy_dtype);
-        if (rcf != PB_ERR_UNSUPPORTED) return rcf;
-    }
-    if (gy_dtype != PB_F32) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "column transform: fp16 planes out of the compiled-plan kernels only");
-#define PB_COLS(MODE, NA)                                                                                        \
-    do {                                                                                                         \
-        int rc = allow_lds(ctx, grad_cols_kernel<MODE, NA, NT>, lds);                                            \
-        if (rc) return rc;                                                                                       \
-        hipLaunchKernelGGL((grad_cols_kernel<MODE, NA, NT>), dim3((unsigned)((blocks + 7) / 8 * 8)), dim3(NT),   \
-                           lds, ctx->stream, planes, gx, gy, H, W, lognb, normalize ? 1 : 0, mm,                 \
-                           planes_per_image, mags, n_angles, discard_sat, thr, (int)blocks, dp, ang);            \
-    } while (0)
-#define PB_COLS_EXT(MODE, NA)                                                                                    \
-    do {                                                                                                         \
-        int rc = allow_lds(ctx, grad_cols_kernel<MODE, NA, 1024, 24>, lds);                                      \
-        if (rc) return rc;                                                                                       \
-        hipLaunchKernelGGL((grad_cols_kernel<MODE, NA, 1024, 24>), dim3((unsigned)((blocks + 7) / 8 * 8)), dim3(1024), \
-                           lds, ctx->stream, planes, gx, gy, H, W, lognb, normalize ? 1 : 0, mm,                 \
-                           planes_per_image, mags, n_angles, discard_sat, thr, (int)blocks, dp, ang);            \
-    } while (0)
-    // (a plan whose widest radix is 18 -- 4320 = 16 x 15 x 18, the 8K height -- runs the variant without 20 and 24: fewer
-    // registers spilled around the butterflies it does take)
-    int maxr = 0;
-    for (int i = 0; i < pl->nstage; ++i) maxr = std::max(maxr, pl->radix[i]);
-    if (ext && mode == 1 && maxr <= 18) {
-        int rc = allow_lds(ctx, grad_cols_kernel<1, 7, 1024, 18>, lds);
+    // the one launch statement of grad_cols_kernel<MODE, NA, NTH, MAXR>
+    auto launch_cols_as = [&](auto kernel, int nth) {
+        int rc = allow_lds(ctx, kernel, lds);
         if (rc) return rc;
-        hipLaunchKernelGGL((grad_cols_kernel<1, 7, 1024, 18>), dim3((unsigned)((blocks + 7) / 8 * 8)), dim3(1024),
-                           lds, ctx->stream, planes, gx, gy, H, W, lognb, normalize ? 1 : 0, mm,
-                           planes_per_image, mags, n_angles, discard_sat, thr, (int)blocks, dp, ang);
-    }
-    else if (ext && mode == 0) PB_COLS_EXT(0, 0);
-    else if (ext) PB_COLS_EXT(1, 7);
-    else if (mode == 0 && nt == 512) {
-        // (192 x 1080p planes: 2.27 -> 1.61 ms against 8-column tiles with 256 threads)
-        int rc = allow_lds(ctx, grad_cols_kernel<0, 0, 1024>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((grad_cols_kernel<0, 0, 1024>), dim3((unsigned)((blocks + 7) / 8 * 8)), dim3(1024),
-                           lds, ctx->stream, planes, gx, gy, H, W, lognb, normalize ? 1 : 0, mm,
-                           planes_per_image, mags, n_angles, discard_sat, thr, (int)blocks, dp, ang);
-    }
-    else if (mode == 0) PB_COLS(0, 0);
-    else if (n_angles == 6 && nt == 512) {
-        // 16-column tiles, one workgroup per CU: 1024 threads (16 waves) hide the stages' LDS latency better than 512
-        // (measured: 4K 62 -> 55 us, 8 x 1080p 113 -> 95 us, 8K 277 -> 268 us)
-        int rc = allow_lds(ctx, grad_cols_kernel<1, 7, 1024>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((grad_cols_kernel<1, 7, 1024>), dim3((unsigned)((blocks + 7) / 8 * 8)), dim3(1024),
-                           lds, ctx->stream, planes, gx, gy, H, W, lognb, normalize ? 1 : 0, mm,
-                           planes_per_image, mags, n_angles, discard_sat, thr, (int)blocks, dp, ang);
-    }
-    else if (n_angles == 6) {
-        // 8-column (or narrower) tiles, two workgroups per CU: 512 threads each (measured against 256: 700x500 31 -> 23 us,
-        // 1080p 56 -> 40 us, 512x512 28 -> 25 us)
-        int rc = allow_lds(ctx, grad_cols_kernel<1, 7, 512>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((grad_cols_kernel<1, 7, 512>), dim3((unsigned)((blocks + 7) / 8 * 8)), dim3(512),
-                           lds, ctx->stream, planes, gx, gy, H, W, lognb, normalize ? 1 : 0, mm,
-                           planes_per_image, mags, n_angles, discard_sat, thr, (int)blocks, dp, ang);
-    }
-    else PB_COLS(1, 0);
-#undef PB_COLS_EXT
-#undef PB_COLS
-    PB_LAUNCH_CHECK();
-    return PB_OK;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((blocks + 7) / 8 * 8)), dim3(nth), lds, ctx->stream, planes, gx, gyf, H, W, lognb,
+                           normalize ? 1 : 0, mm, planes_per_image, mags, n_angles, discard_sat, thr, (int)blocks, dp, ang);
+        PB_LAUNCH_CHECK();
+        return (int)PB_OK;
+    };
+    // (which variant: choose_cols -- the widest radix it must hold, then the threads)
+    if (c.max_radix == 18) return launch_cols_as(grad_cols_kernel<1, 7, 1024, 18>, 1024);
+    if (c.max_radix == 24 && mode == 0) return launch_cols_as(grad_cols_kernel<0, 0, 1024, 24>, 1024);
+    if (c.max_radix == 24) return launch_cols_as(grad_cols_kernel<1, 7, 1024, 24>, 1024);
+    if (mode == 0 && c.threads == 1024) return launch_cols_as(grad_cols_kernel<0, 0, 1024>, 1024);
+    if (mode == 0) return launch_cols_as(grad_cols_kernel<0, 0, NT>, NT);
+    if (n_angles == 6 && c.threads == 1024) return launch_cols_as(grad_cols_kernel<1, 7, 1024>, 1024);
+    if (n_angles == 6) return launch_cols_as(grad_cols_kernel<1, 7, 512>, 512);
+    return launch_cols_as(grad_cols_kernel<1, 0, NT>, NT);
 }
 
 }  // namespace
@@ -1778,14 +1547,22 @@ int pb_fourier_gradients_impl(pb_ctx *ctx, const float *planes, int P, int H, in
 // out_dtype PB_F16: gx / gy are __half planes (pb_gradient_planes_half says whether this context builds them for the shape)
 int pb_fourier_gradients_typed(pb_ctx *ctx, const float *planes, int P, int H, int W, void *gx, void *gy, int out_dtype) {
     if (P <= 0 || H < 2 || W < 2) return pb_fail(ctx, PB_ERR_BADARG, "fourier_gradients: bad shape");
-    if (gx) { int rc = launch_rows(ctx, planes, static_cast<float *>(gx), P, H, W, false, nullptr, 1, out_dtype); if (rc) return rc; }
-    if (gy) { int rc = launch_cols(ctx, planes, nullptr, static_cast<float *>(gy), P, H, W, 0, false, nullptr, 1, nullptr, 0, 0, out_dtype); if (rc) return rc; }
+    const LineUse use = planes_use(out_dtype, false);
+    if (gx) { int rc = launch_rows(ctx, choose_rows(ctx->host_plans, ctx->line, W, H, P, use), planes, gx, P, H, W, false, nullptr, 1, out_dtype); if (rc) return rc; }
+    if (gy) { int rc = launch_cols(ctx, choose_cols(ctx->host_plans, ctx->line, H, W, P, use), planes, nullptr, gy, P, H, W, 0, false, nullptr, 1, nullptr, 0, 0, out_dtype); if (rc) return rc; }
     return PB_OK;
 }
 
+// Both choosers say fp16 planes can be written for the shape, for one plane and for a batch beyond every threshold of theirs
+// (one each, in the number of workgroups): an answer that held for some P only would fail the others' calls outright.
+// (W % 32: the rule from before the choosers, kept so that no shape changes its planes' type -- the choosers would also write
+// fp16 planes at widths 720 and 1200 under the heights from 1200 up, whose widest tile is 16 columns: DESIGN.md 4.4)
 bool pb_gradient_planes_half(pb_ctx *ctx, int H, int W) {
-    return ctx->cols_fixed && ctx->rows_fixed && ctx->fft_first < 0 && ctx->fft_first_rows < 0 &&
-           ctx->fft_ext_radix != 0 && pb_lines_fixed_shape(H, W);
+    const LineUse use = planes_use(PB_F16, false);
+    if (W % 32) return false;
+    for (int P : {1, 4096})
+        if (!choose_rows(ctx->host_plans, ctx->line, W, H, P, use).half_ok || !choose_cols(ctx->host_plans, ctx->line, H, W, P, use).half_ok) return false;
+    return true;
 }
 
 int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H, int W, const pb_options *opt,
@@ -1797,11 +1574,16 @@ int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H
         opt->n_interpolated_angles > PB_MAX_INTERP)
         return pb_fail(ctx, PB_ERR_BADARG, "n_angles / n_interpolated_angles out of range");
     const long HW = (long)H * W;
-    const FftPlan *plh = pb_get_plan(ctx, H);
-    if (!plh) return PB_ERR_NOMEM;
-    const int est_lognb = pick_lognb(ctx, plh, W, B, opt->n_angles == 6, nullptr, opt->n_angles == 6 && !(opt->q > 0.f) && ctx->cols_fixed);   // as launch_cols
-    const int col_tiles = (W + (2 << est_lognb) - 1) / (2 << est_lognb);
-    const int est_tiles = col_tiles;                          // partial maxima per image: one per column tile
+    const bool norm = opt->q > 0.f;                  // q == 0: transforms of the un-normalised image, maxima rescaled afterwards
+    // what the two line transforms run (line_choice.h): the column choice also says how many partial maxima an image has --
+    // one per column tile --, which sizes est.mags and is what the parameter kernel folds
+    LineUse cuse;
+    cuse.maxima = 1; cuse.n_angles = opt->n_angles; cuse.normalize = norm; cuse.discard_sat = opt->discard_saturation;
+    const LineChoice cols = choose_cols(ctx->host_plans, ctx->line, H, W, B, cuse);
+    LineUse guse;
+    guse.C = C; guse.in_dtype = dtype; guse.normalize = norm;
+    const LineChoice gray_rows = choose_rows(ctx->host_plans, ctx->line, W, H, B, guse);
+    const int col_tiles = cols.tiles;
     float *gray = static_cast<float *>(pb_scratch(ctx, "est.gray", sizeof(float) * B * HW));
     float *gx = static_cast<float *>(pb_scratch(ctx, "est.gx", sizeof(float) * B * HW));
     unsigned *mm = static_cast<unsigned *>(pb_scratch(ctx, "est.mm", sizeof(unsigned) * 2 * B));
@@ -1812,12 +1594,12 @@ int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H
     const float2 *part_q0 = nullptr;
     int bpi_q0 = 0;
     // q == 0: gray, its range and the row transform in one launch where the lines allow it
-    bool rows_done = false;
-    if (opt->q <= 0.f) {
+    const bool rows_done = gray_rows.taken != 0;
+    if (rows_done) {
         float2 *pt = nullptr;
-        const int rcg = launch_gray_rows(ctx, in, dtype, B, C, H, W, gray, gx, &pt, &bpi_q0);
-        if (rcg == PB_OK) { rows_done = true; part_q0 = pt; }
-        else if (rcg != PB_ERR_UNSUPPORTED) return rcg;
+        const int rcg = launch_gray_rows(ctx, gray_rows, in, B, C, H, W, gray, gx, &pt, &bpi_q0);
+        if (rcg) return rcg;
+        part_q0 = pt;
     }
     if (!rows_done) {
     ProfScope prof(ctx, PB_PROF_GRAY);
@@ -1865,11 +1647,10 @@ int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H
     }
     PB_LAUNCH_CHECK();
     }
-    const bool norm = opt->q > 0.f;                  // q == 0: transforms of the un-normalised image, maxima rescaled afterwards
     int rc = PB_OK;
-    if (!rows_done) rc = launch_rows(ctx, gray, gx, B, H, W, norm, mm, 1);
+    if (!rows_done) rc = launch_rows(ctx, choose_rows(ctx->host_plans, ctx->line, W, H, B, planes_use(PB_F32, norm)), gray, gx, B, H, W, norm, mm, 1);
     if (rc) return rc;
-    rc = launch_cols(ctx, gray, gx, nullptr, B, H, W, 1, norm, mm, 1, mags, opt->n_angles, opt->discard_saturation);
+    rc = launch_cols(ctx, cols, gray, gx, nullptr, B, H, W, 1, norm, mm, 1, mags, opt->n_angles, opt->discard_saturation);
     if (rc) return rc;
     float *khat = nullptr;
     pb_fft_sel *fsel = nullptr;
@@ -1892,7 +1673,7 @@ int pb_estimate_impl(pb_ctx *ctx, const void *in, int dtype, int B, int C, int H
     const int set1 = khat ? (lean ? KH_SLICES_LEAN + 1 : KH_SLICES) : 1;
     const int set2 = khat2 ? (lean ? KH_SLICES_LEAN : KH_SLICES) : 0;
     hipLaunchKernelGGL(blur_params_kernel, dim3(B, set1 + set2), dim3(NT), 0, ctx->stream, dev_info, mm, mags, wts, opt->n_angles,
-                       opt->n_interpolated_angles, opt->c, opt->b, opt->support, opt->force_theta_deg, est_tiles, ksize,
+                       opt->n_interpolated_angles, opt->c, opt->b, opt->support, opt->force_theta_deg, col_tiles, ksize,
                        (!(ksize & 1) && opt->boundary == PB_WRAP) ? 1 : 0, norm ? nullptr : part_q0, bpi_q0, mm, khat, fsel,
                        ctx->fft_min_phases, spec1, lean, khat2, fsel2, ps2, set2 ? set1 : 0);
     PB_LAUNCH_CHECK();

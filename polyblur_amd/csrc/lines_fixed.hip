@@ -1,7 +1,7 @@
 // The line transforms of the estimation (blur_estimation.py:112-134, filters.py:159-186) for the line lengths whose plan is
 // known when the library is compiled -- the BASELINE sides (columns 2160 = 9 x 16 x 15, 1080 = 6 x 15 x 12, 4320 = 15 x 16 x 18;
 // rows 3840 = 15 x 16 x 16, 1920 = 8 x 16 x 15, 7680 = 16 x 20 x 24) and sixteen common picture sides from 512 to 4096
-// (PB_COLS_PLANS / PB_ROWS_PLANS below), in the stage orders estimate.hip:launch_cols / rows_plan give those lengths:
+// (PB_COLS_PLANS / PB_ROWS_PLANS of line_choice.h), in the stage orders choose_cols / choose_rows give those lengths:
 //   cols_fixed_kernel        the column transform with the directional maxima folded behind it (grad_cols_kernel's MODE 1), or
 //                            storing the y derivative as float / fp16 planes (MODE 0: the gradients halo masking keeps);
 //   gray_rows_fixed_kernel   gray + range partials + the row transform from the image's channels (gray_rows_kernel);
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(NTH) void cols_fixed_kernel(const float *__restrict
 
 // ------------------------------------------------------------------------------------------------------------------------
 // Row transform (one workgroup = one PAIR of rows as one complex line): gray_rows_kernel / grad_rows_kernel<.., true> of
-// estimate.hip for the line lengths 3840 = 15 x 16 x 16, 1920 = 8 x 16 x 15 and 7680 = 16 x 20 x 24 (estimate.hip:rows_plan's
+// estimate.hip for the line lengths 3840 = 15 x 16 x 16, 1920 = 8 x 16 x 15 and 7680 = 16 x 20 x 24 (choose_rows'
 // orders), the same butterflies in the same order.  Beside what a one-plan kernel saves (above), the line sits in LDS with
 // one pad element behind every 32 (PHI): the run-time-plan kernel's innermost stage reads s[16 t + q] from lane t -- a stride
 // of 128 bytes, every second lane on the same banks (61 % of its LDS cycles were bank conflicts, VERDICT r5 #1d) -- and its
@@ -461,7 +461,6 @@ __device__ __forceinline__ void rows_fixed_body(cf *s, IN &in, TO *o0, int W, bo
     PB_LF_EXIT(0);
 }
 
-constexpr int rows_lds_bytes(int n) { return (n + (n >> 5) + 1) * 8; }
 // (the second launch bound = waves per SIMD the register allocation must leave room for: five 256-thread workgroups per CU
 // -- what 31.7 KB of LDS allow a 3840-point line -- are five waves per SIMD)
 constexpr int rows_waves(int n, int nth) {
@@ -512,18 +511,13 @@ __global__ __launch_bounds__(NTH, rows_waves(R0 * R1 * R2, NTH)) void grad_rows_
 
 // whether the line's twiddle table joins the tile in LDS: both (rounded up to whole 1-KB LDS-DMA requests) within what a
 // workgroup of that size may take -- all 160 KB on 1024 threads (one per CU), half of it on 512 (two per CU)
-constexpr bool cols_twlds(int n, int lognb, int nth) {
-    return ((n * (1 << lognb) * 8 + 1023) / 1024 + (n * 8 + 1023) / 1024) * 1024 <= (nth == 1024 ? 160 : 80) * 1024;
-}
-
 template <int R0, int R1, int R2, int LOGNB, int NTH, bool TWLDS>
 int launch_fixed(pb_ctx *ctx, const float *gray, const float *gx, int P, int W, unsigned *mags, bool sat, const FftPlan *pl,
-                 const AngleTable7 &ang, void *gy_out = nullptr, int gy_dtype = PB_F32) {
+                 const AngleTable7 &ang, void *gy_out, int gy_dtype) {
     constexpr int N = R0 * R1 * R2, NB = 1 << LOGNB;
-    constexpr size_t lds = (size_t)((N * NB * 8 + 1023) / 1024) * 1024 + (TWLDS ? (size_t)((N * 8 + 1023) / 1024) * 1024 : 0);
-    static_assert(lds <= 160 * 1024, "tile + twiddle table beyond LDS");
+    constexpr size_t lds = cols_lds_bytes(N, LOGNB, NTH);
+    static_assert(TWLDS == cols_twlds(N, LOGNB, NTH) && lds <= 160 * 1024, "tile + twiddle table beyond LDS");
     const long blocks = (long)P * (W / (2 * NB));
-    if (blocks > 0x7fffffffL) return PB_ERR_UNSUPPORTED;
     const unsigned grid = (unsigned)((blocks + 7) / 8 * 8);
 #define PB_LAUNCH_FIXED(SAT, TGY)                                                                                                \
     do {                                                                                                                         \
@@ -541,100 +535,65 @@ int launch_fixed(pb_ctx *ctx, const float *gray, const float *gx, int P, int W, 
     return PB_OK;
 }
 
+// the one launch statement of the row kernels
+template <class K, class... A> int launch_rows_as(pb_ctx *ctx, K k, long blocks, int nth, size_t lds, A... args) {
+    if (lds > 48 * 1024) PB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(nth), lds, ctx->stream, args...);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+template <int R0, int R1, int R2, int NTH>
+int launch_rows_fixed(pb_ctx *ctx, const float *in, int C, float *gray, void *gx, float2 *part, long blocks, int H, const FftPlan *pl, int gx_dtype) {
+    constexpr size_t lds = rows_lds_bytes(R0 * R1 * R2);
+    if (C == 0 && gx_dtype == PB_F16) return launch_rows_as(ctx, grad_rows_fixed_kernel<R0, R1, R2, NTH, __half>, blocks, NTH, lds, in, static_cast<__half *>(gx), H, pl->tw, pl->drev);
+    if (C == 0) return launch_rows_as(ctx, grad_rows_fixed_kernel<R0, R1, R2, NTH, float>, blocks, NTH, lds, in, static_cast<float *>(gx), H, pl->tw, pl->drev);
+    if (C == 3) return launch_rows_as(ctx, gray_rows_fixed_kernel<R0, R1, R2, NTH, 3>, blocks, NTH, lds, in, gray, static_cast<float *>(gx), part, H, pl->tw, pl->drev);
+    return launch_rows_as(ctx, gray_rows_fixed_kernel<R0, R1, R2, NTH, 1>, blocks, NTH, lds, in, gray, static_cast<float *>(gx), part, H, pl->tw, pl->drev);
+}
+
 }  // namespace
 
-// PB_ERR_UNSUPPORTED: not one of the compiled plans / tile widths (the caller then takes grad_cols_kernel).
+// The launches of a choice of kind PB_LINE_COMPILED (line_choice.h: the choosers ask pb_cols_fixed_has / pb_rows_fixed_has, which
+// answer from the tables these cases are generated from); anything else here is a program error, not a fallback.
 // Which kernel transforms a line must not depend on the batch it arrives in (an image gets the same bits alone and in a
-// batch): every tile width estimate.hip:pick_lognb can give one of these line lengths is compiled -- the wide tile of a grid
-// that fills the chip (1024 threads, one workgroup per CU) and the narrow one of a lone image (512 threads, two per CU) -- and
-// what decides between this file and grad_cols_kernel is the image's own shape and the options alone.
-int pb_launch_cols_fixed(pb_ctx *ctx, const float *gray, const float *gx, int P, int H, int W, int lognb, unsigned *mags,
-                         int n_angles, int discard_sat, const FftPlan *pl, void *gy_out, int gy_dtype) {
-    if ((!gy_out && n_angles != 6) || !pl || pl->bluestein_m || pl->nstage != 3 || pl->n != H || lognb < 1 || (W % (2 << lognb)) != 0)
-        return PB_ERR_UNSUPPORTED;
+// batch): every tile width and thread count the choosers can give one of these line lengths is compiled -- columns: the wide
+// tile of a grid that fills the chip (1024 threads, one workgroup per CU) and the narrow one of a lone image (512 threads, two
+// per CU) -- and what decides between this file and the run-time-plan kernels is the image's own shape and the options alone
+// (tests/test_line_choice_cpu.py sweeps the choosers for both).
+int pb_launch_cols_fixed(pb_ctx *ctx, const LineChoice &c, const float *gray, const float *gx, int P, int W, unsigned *mags,
+                         int n_angles, const FftPlan *pl, void *gy_out, int gy_dtype) {
     AngleTable7 ang;
     pb_angle_table(n_angles, ang.cs, ang.sn, 7);
-    const int r0 = pl->radix[0], r1 = pl->radix[1], r2 = pl->radix[2];
-    const bool sat = discard_sat != 0;
-    // The compiled plans: line length = R0 x R1 x R2 in the order launch_cols gives it (smallest radix from 5 up -- or the one whose
-    // butterflies are one trip -- first), with the two tile widths pick_lognb can give that length: NARROW on 512 threads (two
-    // workgroups per CU) and WIDE on 1024 (one), 0 = that width does not occur.  The BASELINE lengths first; then the common
-    // picture sizes (720p, 1440p, 2K ...), where the same kernels run 1.3 - 2 x faster than the run-time-plan ones.
-    // The twiddle table joins the tile in LDS where both fit (cols_twlds).
-#define PB_COLS_PLANS(X)                                                                          \
-    X(2160, 9, 16, 15, 2, 3) X(1080, 6, 15, 12, 3, 4) X(4320, 15, 16, 18, 1, 2)                    \
-    X(512, 2, 16, 16, 3, 4) X(640, 4, 16, 10, 3, 4) X(720, 3, 16, 15, 3, 4) X(768, 3, 16, 16, 3, 4) \
-    X(800, 5, 16, 10, 3, 4) X(960, 4, 16, 15, 3, 4) X(1024, 4, 16, 16, 3, 4) X(1200, 5, 16, 15, 3, 0) \
-    X(1280, 5, 16, 16, 3, 0) X(1440, 6, 16, 15, 2, 3) X(1536, 6, 16, 16, 2, 3) X(1600, 10, 16, 10, 2, 3) \
-    X(2048, 8, 16, 16, 2, 3) X(2560, 10, 16, 16, 2, 0) X(3072, 12, 16, 16, 1, 2) X(4096, 16, 16, 16, 1, 2)
+    const bool sat = c.sat != 0;
+    // (the twiddle table joins the tile in LDS where both fit: cols_twlds)
 #define PB_COLS_CASE(N_, R0, R1, R2, LN, LW)                                                                                   \
-    if (H == N_ && r0 == R0 && r1 == R1 && r2 == R2) {                                                                         \
-        if (LW != 0 && lognb == LW) return launch_fixed<R0, R1, R2, (LW ? LW : 1), 1024, cols_twlds(N_, (LW ? LW : 1), 1024)>(ctx, gray, gx, P, W, mags, sat, pl, ang, gy_out, gy_dtype); \
-        if (lognb == LN) return launch_fixed<R0, R1, R2, LN, 512, cols_twlds(N_, LN, 512)>(ctx, gray, gx, P, W, mags, sat, pl, ang, gy_out, gy_dtype); \
+    if (c.kind == PB_LINE_COMPILED && plan_is(*pl, N_, R0, R1, R2)) {                                                          \
+        if (LW != 0 && c.lognb == LW) return launch_fixed<R0, R1, R2, (LW ? LW : 1), 1024, cols_twlds(N_, (LW ? LW : 1), 1024)>(ctx, gray, gx, P, W, mags, sat, pl, ang, gy_out, gy_dtype); \
+        if (c.lognb == LN) return launch_fixed<R0, R1, R2, LN, 512, cols_twlds(N_, LN, 512)>(ctx, gray, gx, P, W, mags, sat, pl, ang, gy_out, gy_dtype); \
     }
     PB_COLS_PLANS(PB_COLS_CASE)
 #undef PB_COLS_CASE
-    return PB_ERR_UNSUPPORTED;
+    return pb_fail(ctx, PB_ERR_UNSUPPORTED, "column transform: no compiled kernel for this choice (%d-sample lines, tiles of %d columns)", pl->n, 2 << c.lognb);
 }
 
-// The row transform of W-sample lines with the plan compiled in; C == 0: a float plane as it is (in = P planes of H x W),
-// else gray + range partials + transform from the image's C channels (in = B images; part: B x pairs partials).
-// nth: the thread count estimate.hip:rows_threads gives the launch.  PB_ERR_UNSUPPORTED: not compiled -- the caller runs its own.
-int pb_launch_rows_fixed(pb_ctx *ctx, const float *in, int C, float *gray, void *gx, float2 *part, long images, int H, int W, int nth,
+// The row transform of W-sample lines with the plan compiled in; C == 0: a float plane as it is (in = P planes of H x W,
+// gx_dtype = PB_F32 | PB_F16 planes out), else gray + range partials + transform from the image's C channels (in = B images;
+// part: B x pairs partials).
+int pb_launch_rows_fixed(pb_ctx *ctx, const LineChoice &c, const float *in, int C, float *gray, void *gx, float2 *part, long images, int H,
                          const FftPlan *pl, int gx_dtype) {
-    if (gx_dtype != PB_F32 && !(gx_dtype == PB_F16 && C == 0)) return PB_ERR_UNSUPPORTED;
-    if (!pl || pl->bluestein_m || pl->nstage != 3 || pl->n != W || (C != 0 && C != 1 && C != 3)) return PB_ERR_UNSUPPORTED;
-    const long blocks = images * ((H + 1) / 2);
-    if (blocks > 0x7fffffffL || blocks < 1) return PB_ERR_UNSUPPORTED;
-    const int r0 = pl->radix[0], r1 = pl->radix[1], r2 = pl->radix[2];
-#define PB_ROWS_FIXED(R0, R1, R2, NTH)                                                                                              \
-    do {                                                                                                                            \
-        constexpr size_t lds = rows_lds_bytes(R0 * R1 * R2);                                                                        \
-        if (C == 0 && gx_dtype == PB_F16) {                                                                                         \
-            auto k = grad_rows_fixed_kernel<R0, R1, R2, NTH, __half>;                                                               \
-            if (lds > 48 * 1024) PB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(NTH), lds, ctx->stream, in, static_cast<__half *>(gx), H, pl->tw, pl->drev); \
-        } else if (C == 0) {                                                                                                        \
-            auto k = grad_rows_fixed_kernel<R0, R1, R2, NTH, float>;                                                                \
-            if (lds > 48 * 1024) PB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(NTH), lds, ctx->stream, in, static_cast<float *>(gx), H, pl->tw, pl->drev); \
-        } else if (C == 3) {                                                                                                        \
-            auto k = gray_rows_fixed_kernel<R0, R1, R2, NTH, 3>;                                                                    \
-            if (lds > 48 * 1024) PB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(NTH), lds, ctx->stream, in, gray, static_cast<float *>(gx), part, H, pl->tw, pl->drev);    \
-        } else {                                                                                                                    \
-            auto k = gray_rows_fixed_kernel<R0, R1, R2, NTH, 1>;                                                                    \
-            if (lds > 48 * 1024) PB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(NTH), lds, ctx->stream, in, gray, static_cast<float *>(gx), part, H, pl->tw, pl->drev);    \
-        }                                                                                                                           \
-        PB_LAUNCH_CHECK();                                                                                                          \
-        return PB_OK;                                                                                                               \
-    } while (0)
-    // (the compiled plans, in the order rows_plan gives them: the BASELINE widths, then the common picture widths)
-#define PB_ROWS_PLANS(X)                                                                         \
-    X(3840, 15, 16, 16) X(1920, 8, 16, 15)                                                       \
-    X(512, 2, 16, 16) X(640, 4, 16, 10) X(720, 3, 16, 15) X(768, 3, 16, 16) X(800, 5, 16, 10) X(960, 4, 16, 15) \
-    X(1024, 4, 16, 16) X(1200, 5, 16, 15) X(1280, 5, 16, 16) X(1440, 6, 16, 15) X(1536, 6, 16, 16) X(1600, 10, 16, 10) \
-    X(2048, 8, 16, 16) X(2560, 10, 16, 16) X(3072, 12, 16, 16) X(4096, 16, 16, 16)
-#define PB_ROWS_CASE(N_, R0, R1, R2)                                   \
-    if (W == N_ && r0 == R0 && r1 == R1 && r2 == R2) {                 \
-        if (nth == 256) PB_ROWS_FIXED(R0, R1, R2, 256);                \
-        if (nth == 128) PB_ROWS_FIXED(R0, R1, R2, 128);                \
+    const long blocks = images * c.tiles;
+#define PB_ROWS_CASE(N_, R0, R1, R2)                                                                                               \
+    if (c.kind == PB_LINE_COMPILED && plan_is(*pl, N_, R0, R1, R2)) {                                                              \
+        if (c.threads == 256) return launch_rows_fixed<R0, R1, R2, 256>(ctx, in, C, gray, gx, part, blocks, H, pl, gx_dtype);      \
+        if (c.threads == 128) return launch_rows_fixed<R0, R1, R2, 128>(ctx, in, C, gray, gx, part, blocks, H, pl, gx_dtype);      \
     }
+#define PB_ROWS_CASE_8K(N_, R0, R1, R2)                                                                                            \
+    if (c.kind == PB_LINE_COMPILED && plan_is(*pl, N_, R0, R1, R2) && c.threads == 512)                                            \
+        return launch_rows_fixed<R0, R1, R2, 512>(ctx, in, C, gray, gx, part, blocks, H, pl, gx_dtype);
     PB_ROWS_PLANS(PB_ROWS_CASE)
+    PB_ROWS_PLAN_8K(PB_ROWS_CASE_8K)
 #undef PB_ROWS_CASE
-    if (W == 7680 && r0 == 16 && r1 == 20 && r2 == 24 && nth == 512) PB_ROWS_FIXED(16, 20, 24, 512);
-#undef PB_ROWS_FIXED
-    return PB_ERR_UNSUPPORTED;
-}
-
-bool pb_lines_fixed_shape(int H, int W) {
-    bool h = false, w = W == 7680;
-#define PB_H_CASE(N_, R0, R1, R2, LN, LW) h = h || H == N_;
-#define PB_W_CASE(N_, R0, R1, R2) w = w || W == N_;
-    PB_COLS_PLANS(PB_H_CASE)
-    PB_ROWS_PLANS(PB_W_CASE)
-#undef PB_H_CASE
-#undef PB_W_CASE
-    return h && w && (W % 32) == 0;
+#undef PB_ROWS_CASE_8K
+    return pb_fail(ctx, PB_ERR_UNSUPPORTED, "row transform: no compiled kernel for this choice (%d-sample lines, %d threads)", pl->n, c.threads);
 }

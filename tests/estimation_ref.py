@@ -356,7 +356,7 @@ def quantised(H, W, levels, seed=11, dtype=np.float32, heavy=0.7):
 # ---------------------------------------------------------------------------------------------
 COLS_PLANS = (2160, 1080, 4320, 512, 640, 720, 768, 800, 960, 1024, 1200, 1280, 1440, 1536, 1600, 2048, 2560, 3072, 4096)
 # height -> (lognb of the narrow tile, of the wide tile) of the plans PB_COLS_PLANS compiles a wide (1024-thread) instance for;
-# 1080 never takes it (pick_lognb keeps 16 columns where W % 16 == 0, the plan refuses other widths), 1200, 1280 and 2560 have none
+# 1080 never takes it (choose_cols keeps 16 columns where W % 16 == 0, the plan refuses other widths), 1200, 1280 and 2560 have none
 WIDE_PLANS = {2160: (2, 3), 4320: (1, 2), 512: (3, 4), 640: (3, 4), 720: (3, 4), 768: (3, 4), 800: (3, 4), 960: (3, 4), 1024: (3, 4),
               1440: (2, 3), 1536: (2, 3), 1600: (2, 3), 2048: (2, 3), 3072: (1, 2), 4096: (1, 2)}
 ANGLE_COUNTS = (1, 2, 3, 5, 7, 12)
@@ -433,7 +433,7 @@ def cases():
     for H in COLS_PLANS:
         out.append(_planted_case("fixed_narrow", 2, 1, H, 32, ("last_row", "last_col"), both))
         out.append(_planted_case("fixed_narrow", 2, 1, H, 32, ("first_row", "br"), both, phi=0.2, discard_saturation=True))
-    # -- ... wide tile: the smallest batch and width with P * (W / (4 << lognb)) >= 200 (pick_lognb), the ridge in the last image's
+    # -- ... wide tile: the smallest batch and width with P * (W / (4 << lognb)) >= 200 (line_choice.h: choose_cols), the ridge in the last image's
     # last tile
     wide = ("middle", "tl", "last_row", "first_col", "middle", "first_row", "last_col", "br")
     for H, (narrow, wide_lognb) in WIDE_PLANS.items():
@@ -452,7 +452,7 @@ def cases():
                 continue
             for H, W in ((37, 75), (64, 96), (1080, 32)):
                 out.append(_planted_case("angles", 1, 1, H, W, "br", tag="a%d_i%d_" % (na, ni), n_angles=na, n_interp=ni))
-    # (the plan of a height with a radix above 16 -- 3240 = 9 x 15 x 24 -- is chosen by launch_cols' ext_variant: not for n_angles != 6)
+    # (the plan of a height with a radix above 16 -- 3240 = 9 x 15 x 24 -- is chosen by choose_cols' ext_variant: not for n_angles != 6)
     out.append(_planted_case("angles", 1, 1, 3240, 24, "br", tag="a12_i30_", n_angles=12, n_interp=30))
     out.append(_planted_case("angles", 1, 1, 4320, 32, "br", tag="a5_i64_", n_angles=5, n_interp=64))
     # -- the mask -------------------------------------------------------------------------------------------------------------------

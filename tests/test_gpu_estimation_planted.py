@@ -120,13 +120,13 @@ def test_where_the_maxima_are_taken_compiled_plans_narrow_tile(engines, case):
 @pytest.mark.parametrize("case", _ids("fixed_wide"), ids=repr)
 def test_where_the_maxima_are_taken_compiled_plans_wide_tile(engines, case):
     """the 15 heights PB_COLS_PLANS compiles a wide (1024-thread) instance for (er.WIDE_PLANS), B = 8 and W = 25 * (4 << lognb): the
-    smallest batch and width with P * (W / (4 << lognb)) >= 200 (pick_lognb), W a multiple of the wide tile; the images have their
+    smallest batch and width with P * (W / (4 << lognb)) >= 200 (line_choice.h: choose_cols), W a multiple of the wide tile; the images have their
     ridges in different places, the last one in its last tile's last column and last row.  Not reached: 1080-point columns (they
-    never take a wide tile with the compiled plans: pick_lognb keeps 16 columns where W % 16 == 0, and the plan is refused where
+    never take a wide tile with the compiled plans: choose_cols keeps 16 columns where W % 16 == 0, and the plan is refused where
     it is not); 1200, 1280 and 2560 (no wide instance is compiled)."""
     B, _, H, W = er.image(case).shape
     narrow, wide = er.WIDE_PLANS[H]
-    assert B * (W // (4 << narrow)) >= 200 and W % (2 << wide) == 0    # what the case is for: pick_lognb takes the wide tile
+    assert B * (W // (4 << narrow)) >= 200 and W % (2 << wide) == 0    # what the case is for: choose_cols takes the wide tile
     run_case(engines, case)
 
 
@@ -136,7 +136,7 @@ def test_long_lines_and_many_tiles(engines, case):
     columns (8200 x 10, 20736 x 10: grad_cols_long_kernel<1>), and 8 x 8200: 513 column tiles of 16, the ridge in the last one --
     blur_params_kernel folds them in two batches of 128 uint4"""
     if case.id.endswith("8x8200_last_col"):
-        # pick_lognb starts from lognb = 3 (16 columns) and only lowers it, but for the wide tile, which needs a plan of two stages
+        # choose_cols starts from lognb = 3 (16 columns) and only lowers it, but for the wide tile, which needs a plan of two stages
         # and more: 8 is one radix-8 stage.  No tile is wider than 16 columns, so there are at least 513
         assert (8200 + 15) // 16 > 512
     run_case(engines, case)
@@ -146,7 +146,7 @@ def test_long_lines_and_many_tiles(engines, case):
 def test_direction_counts(engines, case):
     """n_angles in {1, 2, 3, 5, 7, 12} x n_interpolated_angles in {7, 30, 64} (less (1, 64): er.DROPPED_GRIDS) on 37 x 75, 64 x 96 and
     1080 x 32, where the compiled plan must refuse (n_angles != 6) and grad_cols_kernel<1, 0> run with the run-time count; 12 at
-    3240 x 24 and 5 at 4320 x 32, heights with a radix above 16, whose plan launch_cols' ext_variant then does not choose.  In 21
+    3240 x 24 and 5 at 4320 x 32, heights with a radix above 16, whose plan choose_cols' ext_variant then does not choose.  In 21
     of these cases (er.gauges: exact_tie) theta, i_min and sigma are fixed by the grid; mags, interp and rho are not"""
     run_case(engines, case)
 
@@ -174,7 +174,7 @@ def test_saturation_mask(engines, case):
 @pytest.mark.parametrize("case", _ids("range"), ids=repr)
 def test_gray_range(engines, case):
     """er.extremes: the minimum and the maximum at the first pixel, the last pixel, in the unpaired last row, in the last row pair.
-    gray_rows_kernel: fp32 at 33 x 45 (45 = 9 x 5: two stages; a prime width such as 47 is Bluestein, which launch_gray_rows
+    gray_rows_kernel: fp32 at 33 x 45 (45 = 9 x 5: two stages; a prime width such as 47 is Bluestein, which choose_rows
     refuses) with C = 1, 3 and a batch of 3 whose images have different ranges, 34 x 48 with C = 4; the compiled row plans at 33 x
     1920 and 33 x 3840 (and PB_ROWS_FIXED=0).  gray_minmax_kernel: the same fp32 cases on PB_EST_GRAY_ROWS=0, fp16 and u8 with HW %
     4 zero (34 x 48: VEC) and not (33 x 45), C = 1 and 3"""

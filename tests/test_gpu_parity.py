@@ -55,7 +55,7 @@ def test_fourier_gradients_sizes(eng, shape):
                                    (1, 1, 12, 6480), (1, 1, 5400, 16)])
 def test_fourier_gradients_extended_radices(eng, shape):
     """lines whose plan takes radices 18 / 20 / 24 to save a stage (4320 = 16 x 15 x 18, 7680 = 16 x 20 x 24 -- the 8K sides --,
-    3240, 5400, 6480): the 512-thread row variant and the 1024-thread column variants (csrc/estimate.hip: factorize,
+    3240, 5400, 6480): the 512-thread row variant and the 1024-thread column variants (csrc/line_choice.h: factorize,
     plan_ext); the other kernel variants keep the greedy plan of the same length"""
     rng = np.random.default_rng(13)
     x = rng.random(shape, dtype=np.float32)

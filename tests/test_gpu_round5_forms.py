@@ -243,7 +243,7 @@ def test_zero_boundary_ring_at_the_default_threshold(engines):
     assert np.abs(a1 - ref.polyblur_deblurring(x, n_iter=1, method="direct", **KW)).max() < 2e-5
 
 
-# ---- which of a plan's radices the line transforms' first / last stage take (csrc/estimate.hip: rows_plan, launch_cols) ----
+# ---- which of a plan's radices the line transforms' first / last stage take (csrc/line_choice.h: choose_rows, choose_cols) ----
 STAGE_ORDER_SHAPES = [(1, 1, 512, 512), (1, 1, 720, 1280), (1, 1, 1080, 1920), (1, 1, 700, 500), (1, 1, 1200, 1280),
                       (1, 1, 1024, 2048), (1, 1, 2160, 1440), (3, 1, 600, 360)]
 
@@ -268,15 +268,22 @@ def test_stage_order_of_the_line_transforms(engines, greedy_engine, shape):
         assert np.abs(a - b).max() < 4e-6 * scale, float(np.abs(a - b).max())
 
 
-def test_stage_order_does_not_depend_on_the_batch(engines):
+@pytest.mark.parametrize("shape,dtype,images,kw", [((12, 3, 360, 640), np.float32, (0, 7, 11), {}),
+                                                   ((12, 3, 512, 640), np.float16, (0, 11), {"remove_halo": True})],
+                         ids=["fp32_360x640", "fp16_remove_halo_512x640"])
+def test_stage_order_does_not_depend_on_the_batch(engines, shape, dtype, images, kw):
     """the order of the stages decides the roundings, so it is a function of the line length alone: an image's records and
-    output are the same bits alone (256-thread row workgroups, 512-thread column workgroups) and in a batch (128 / 1024)"""
-    B, C, H, W = 12, 3, 360, 640
+    output are the same bits alone (256-thread row workgroups, 512-thread column workgroups) and in a batch (128 / 1024).
+    fp16 with remove_halo at 512 x 640 -- the smallest height and width both compiled tables hold, the shape class where the
+    gradient planes halo masking keeps are fp16 planes out of the compiled kernels (tests/test_gpu_halo.py) --: the batch of 12
+    crosses both thresholds (12 x 256 row pairs > 1280 workgroups, 12 x 20 column tiles >= 200)"""
+    B, C, H, W = shape
     x, _ = synthetic_blurry_batch(B, C, H, W, seed0=5)
+    x = x.astype(dtype)
     eng = engines["default"]
-    full, infos = _run(eng, x, n_iter=2, **KW)
-    for i in (0, 7, 11):
-        one, oinfos = _run(eng, x[i:i + 1], n_iter=2, **KW)
+    full, infos = _run(eng, x, n_iter=2, **KW, **kw)
+    for i in images:
+        one, oinfos = _run(eng, x[i:i + 1], n_iter=2, **KW, **kw)
         assert np.array_equal(full[i:i + 1], one), i
         for k in range(2):
             for f in ("mags", "theta", "sigma", "rho"):
