@@ -12,6 +12,11 @@
  *   - plain C, no torch / pybind types; every image pointer is a DEVICE pointer to a
  *     contiguous NCHW array (the reference's (B,C,H,W) tensors); `float *host_*`
  *     arguments are HOST pointers and make the call synchronise the stream;
+ *   - a device pointer needs the alignment of its element type and no more (4 bytes for
+ *     float planes and records, 2 for fp16, 1 for 8-bit planes): a view at any element
+ *     offset of a larger buffer is a valid operand.  The 16-byte paths are taken where the
+ *     pitches -- and, in the four launchers that look at them, the addresses -- allow,
+ *     and give the results of the aligned operand;
  *   - all other calls are asynchronous on the context's stream;
  *   - the caller owns every buffer; inputs are never written; scratch memory lives in
  *     the context; a context runs on one stream at a time and is not thread-safe (one
