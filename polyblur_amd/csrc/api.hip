@@ -86,8 +86,12 @@ static int pitch4(int w) { return (w + 3) & ~3; }
 //   PB_POLY_ALWAYS=0            never PolySpec.always (issue every launch the records might need)
 //   PB_EST_GRAY_ROWS=0|1|2      gray + range + row transform in one launch: never | fp32 lines up to 4096 | any line in LDS
 //   PB_EST_LEAN=0               the parameter kernel forms the whole record before the spectra (no short chain)
-//   PB_DT_ROWS_REG=0            the domain-transform row pass through global memory instead of registers
-//   PB_DT_COLS_STRIP=0          the domain-transform column pass as two sweeps through global memory instead of strips
+//   PB_DT_ROWS_REG=0|1|2|3      the domain transform's first row pass (dt_choice.h): through global memory | the row in registers, on one wave
+//                               or -- up to 8192 rows in the batch -- over the four waves of a workgroup | one wave always | four waves always
+//   PB_DT_COLS_STRIP=0|1|2      its column pass by one thread per column: two sweeps through global memory | strips, the weights stored
+//                               where that pays (three fp32 channels, 128 rows and up) | strips, the weights always formed from J again
+//   PB_DT_COLS_COOP=0|1|2       its column pass by workgroups of 16 (one channel: 64) columns through LDS: never | up to 24576 columns
+//                               in the batch | always where rows and operands lie on 16-byte boundaries
 //   PB_FFT_EXT_RADIX=0          greedy transform plans only (radices up to 16)
 //   PB_FFT_FIRST / _ROWS=0|r    the column / row transform's first and last stage: the greedy plan's order, or radix r (default: by line length)
 //   PB_COLS_FIXED=0, PB_ROWS_FIXED=0   the line transforms always by the run-time-plan kernels (estimate.hip), also where
@@ -108,7 +112,7 @@ static void pb_read_knobs(pb_ctx *ctx) {
 #ifdef PB_EXPERIMENTAL
     geti("PB_STRIP", ctx->strip_mode);
 #endif
-    geti("PB_EST_GRAY_ROWS", ctx->line.est_gray_rows); geti("PB_EST_LEAN", ctx->est_lean); geti("PB_DT_ROWS_REG", ctx->dt_rows_reg); geti("PB_DT_COLS_STRIP", ctx->dt_cols_strip); geti("PB_DT_COLS_COOP", ctx->dt_cols_coop);
+    geti("PB_EST_GRAY_ROWS", ctx->line.est_gray_rows); geti("PB_EST_LEAN", ctx->est_lean); geti("PB_DT_ROWS_REG", ctx->dt.rows_reg); geti("PB_DT_COLS_STRIP", ctx->dt.cols_strip); geti("PB_DT_COLS_COOP", ctx->dt.cols_coop);
     geti("PB_FFT_EXT_RADIX", ctx->line.fft_ext_radix); geti("PB_FFT_FIRST", ctx->line.fft_first); geti("PB_FFT_FIRST_ROWS", ctx->line.fft_first_rows); geti("PB_COLS_FIXED", ctx->line.cols_fixed); geti("PB_ROWS_FIXED", ctx->line.rows_fixed);
     geti("PB_POLY1", ctx->poly_mode); geti("PB_POLY_TALL", ctx->poly_tall); geti("PB_POLY_ONE_LAUNCH", ctx->poly_one_launch);
     geti("PB_POLY_ALWAYS", ctx->poly_always); geti("PB_POLY_PADDED", ctx->poly_padded); geti("PB_TAPER_RING", ctx->taper_ring); geti("PB_ZERO_RING", ctx->zero_ring); getl("PB_ZERO_RING_MIN_PAIRS", ctx->zero_ring_min_pairs);
@@ -128,6 +132,22 @@ extern "C" int pb_debug_line_choice(int axis, int n, int other, int P, const int
     const int head[13] = {c.kind, c.taken, c.threads, c.lognb, c.tiles, c.lds, c.max_radix, c.sat, c.half_ok, c.ext, c.first, c.plan.bluestein_m, c.plan.nstage};
     std::copy(head, head + 13, out);
     std::copy(c.plan.radix, c.plan.radix + 24, out + 13);
+    return PB_OK;
+}
+
+// What the domain-transform filter would run for one call on B images of C (1 or 3) channels, H x W samples of elem (4 or 2)
+// bytes (dt_choice.h: choose_dt); host only, no device needed.  self_guided: the joint image is the input itself; aligned16: the
+// joint image and the output lie on 16-byte boundaries.  knobs: PB_DT_ROWS_REG, PB_DT_COLS_STRIP, PB_DT_COLS_COOP as three ints
+// -- the choice of an engine built under those --, or null: as pb_create reads the environment.  out (7): the row form of the
+// first iteration, its chunks, the column form, its strip / block rows, the floats of "dt.carry" and "dt.weights", dynamic LDS.
+extern "C" int pb_debug_dt_choice(int elem, int C, int B, int H, int W, int self_guided, int aligned16, const int *knobs, long long *out) {
+    if ((elem != 4 && elem != 2) || (C != 1 && C != 3) || B < 1 || H < 1 || W < 1 || !out) return PB_ERR_BADARG;
+    pb_ctx ctx;
+    pb_read_knobs(&ctx);
+    const DtKnobs k = knobs ? DtKnobs{knobs[0], knobs[1], knobs[2]} : ctx.dt;
+    const DtChoice c = choose_dt(k, elem, C, B, H, W, self_guided != 0, aligned16 != 0);
+    const long long v[7] = {c.rows, c.chunks, c.cols, c.cols_rows, c.carry, c.weights, c.lds};
+    std::copy(v, v + 7, out);
     return PB_OK;
 }
 

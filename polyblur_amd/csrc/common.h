@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/polyblur_hip.h"
+#include "dt_choice.h"
 #include "line_choice.h"
 
 
@@ -171,9 +172,7 @@ struct pb_ctx {
     int taper_ring = 1;                  // env PB_TAPER_RING: 0 = every blend of an edgetaper covers the whole padded plane
     int poly_padded = 1;                 // env PB_POLY_PADDED: 0 = a polynomial whose operand is a padded plane (after an edgetaper) keeps three Horner steps
     int est_lean = 1;                    // env PB_EST_LEAN: 0 = the parameter kernel always forms the whole record before the spectra
-    int dt_cols_strip = 1;               // env PB_DT_COLS_STRIP: 0 = the domain-transform column pass as two sweeps through global memory (dt_cols_fused_kernel), 2 = strips whose up sweep always forms the weights from J again (dt_cols_up_kernel)
-    int dt_cols_coop = 1;                // env PB_DT_COLS_COOP: 0 = never the few-columns form of the column pass (dt_cols_coop_kernel), 2 = always where it applies
-    int dt_rows_reg = 1;                 // env PB_DT_ROWS_REG: 0 = the domain-transform row pass always through global memory (dt_rows_fused_kernel), 2 = registers, one wave per row always, 3 = a row over four waves always (dt_rows_regw_kernel)
+    DtKnobs dt;                          // env PB_DT_ROWS_REG, PB_DT_COLS_STRIP, PB_DT_COLS_COOP: what the domain transform's choice reads (dt_choice.h)
     int poly_always = 1;                 // env PB_POLY_ALWAYS: 0 = never PolySpec.always (every polynomial issues all the launches its records might need)
     LineKnobs line;                      // env PB_EST_GRAY_ROWS, PB_FFT_EXT_RADIX, PB_FFT_FIRST, PB_FFT_FIRST_ROWS, PB_COLS_FIXED, PB_ROWS_FIXED: what the line transforms' choice reads (line_choice.h)
     // tuning / comparison knobs of single kernels, read once in pb_create (the table of every knob: api.hip, pb_read_knobs)

@@ -255,8 +255,9 @@ _PREFILTER = {"bilateral": capi.PB_PREFILTER_BILATERAL, "domain_transform": capi
 
 def _polyblur_halo(prefilter, method="fft", dtype=F32):
     """remove_halo=True, prefiltering=True on halo_ref's pipeline image (1,3,24,40), whose mask finds work (tests/test_gpu_halo.py::
-    test_blind_pipeline_fp32; hr.TOL_PIPE / TOL_PIPE_HALF): filters.hip:1154 (pb_halo_apply: x, out and the recombination operands),
-    :1136, and the prefilter's own launches (bilateral.hip, filters.hip:968,1254, nc.hip)"""
+    test_blind_pipeline_fp32; hr.TOL_PIPE / TOL_PIPE_HALF): filters.hip: pb_halo_apply (x, out and the recombination operands)
+    and pb_grad_energy, and the prefilter's own launches (bilateral.hip, nc.hip; dt.hip: dt_cols_coop_kernel's 16-byte requests,
+    which dt_choice.h: choose_dt grants to operands on 16-byte boundaries alone)"""
     x, want = _halo_oracle(prefilter, method, dtype == F16)
     shape = x.shape
     kw = dict(hr.PIPE_KW, n_iter=2)
@@ -619,7 +620,7 @@ for _c in ("5x5_on_200x300-fft", "7x7_planes_on_33x40-direct", "25x25_on_64x64-f
 # pb_halo_mask and its backward
 # ---------------------------------------------------------------------------------------------
 def _halo_mask(shape):
-    """each of its five pointers (tests/test_gpu_halo.py::test_stage: hr.TOL_STAGE against float64).  filters.hip:1136 takes
+    """each of its five pointers (tests/test_gpu_halo.py::test_stage: hr.TOL_STAGE against float64).  filters.hip: pb_grad_energy takes
     grad_energy_kernel's scalar form where gx or gy is off a 16-byte boundary, and its partial sums then add up in another order:
     for those runs (a) stands alone"""
     s = hr.stage_set(shape)
@@ -635,7 +636,7 @@ def _halo_mask(shape):
                 sums=lambda offs: bool(offs.get("gx") or offs.get("gy")))
 
 
-case("halo-mask-32x48", shape=(1, 3, 32, 48))(_halo_mask)              # four samples per lane (filters.hip:1154)
+case("halo-mask-32x48", shape=(1, 3, 32, 48))(_halo_mask)              # four samples per lane (filters.hip: pb_halo_apply)
 case("halo-mask-96x128", shape=(1, 1, 96, 128))(_halo_mask)            # more than one block per plane in the energy sum
 
 
@@ -719,7 +720,7 @@ case("bilateral-backward-k7", ksize=7)(_bilateral_backward)
 
 def _recursive(shape, dtype=F32, joint=False, engine="default", n=2):
     """pb_dt_recursive_filter against the oracle: 5e-6, float16 images 1e-3 (tests/test_gpu_edge_aware.py::test_recursive_filter,
-    ::test_recursive_filter_joint_image).  C = 1 and 3 run the fused kernels (filters.hip:1217-1297), C = 4 the domain planes"""
+    ::test_recursive_filter_joint_image).  C = 1 and 3 run the fused kernels (dt.hip: dt_filter_fused, in the forms dt_choice.h chooses), C = 4 the domain planes"""
     x = ea.image(shape, seed=17).astype(NP[dtype])
     j = ea.image(shape, seed=6).astype(NP[dtype]) if joint else None
     want = ref.recursive_filter(x.astype(np.float32), 6.0, 0.4, n, None if j is None else j.astype(np.float32))
@@ -742,7 +743,7 @@ for _sh, _n in (((1, 1, 33, 72), "c1"), ((2, 3, 21, 64), "c3"), ((1, 4, 21, 64),
         case("recursive-%s%s" % (_n, _t), shape=_sh, dtype=_dt)(_recursive)
         case("recursive-%s-joint%s" % (_n, _t), shape=_sh, dtype=_dt, joint=True)(_recursive)
         if _n != "c4":
-            # filters.hip:968,1254 (dt_cols_coop_kernel, PB_DT_COLS_COOP=2: the column pass whose lanes fetch J by 16-byte LDS-DMA)
+            # dt.hip: dtc_dma16, dt_choice.h: choose_dt's aligned16 (dt_cols_coop_kernel, PB_DT_COLS_COOP=2: the column pass whose lanes fetch J by 16-byte LDS-DMA)
             case("recursive-%s-coop%s" % (_n, _t), shape=_sh, dtype=_dt, engine="coop")(_recursive)
             case("recursive-%s-coop-joint%s" % (_n, _t), shape=_sh, dtype=_dt, joint=True, engine="coop")(_recursive)
 

@@ -6,7 +6,7 @@
 * PolySpec.always (PB_POLY_ALWAYS, csrc/conv.hip: pb_launch_conv_poly): two window launches per polynomial and nothing else
   for large images under the wrap boundary -- against the call that issues every launch its records might need, and
   against the oracle (deblurring.py:139-169);
-* the domain-transform row pass with the row in registers (PB_DT_ROWS_REG, csrc/filters.hip: dt_rows_reg_kernel): bit-identical
+* the domain-transform row pass with the row in registers (PB_DT_ROWS_REG, csrc/dt.hip: dt_rows_reg_kernel): bit-identical
   to the pass through global memory (domain_transform.py:56-85);
 * method='direct' (the zero boundary, filters.py:40-49; the reference's own choice on a GPU, main.py:109-112) as one window
   pass plus three Horner steps over the border ring (PB_ZERO_RING, csrc/conv.hip + conv_wfft.hip: ring_live) against three
@@ -20,6 +20,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import polyblur_ref as ref                      # the checker (tests only)
 from polyblur_amd.synthetic import synthetic_blurry_batch
+
+import dt_form_cases as dt_cases                            # shapes and knob sets of the domain-transform form tests
 
 
 def _engine(**env):
@@ -39,7 +41,8 @@ def _engine(**env):
 @pytest.fixture(scope="module")
 def engines():
     return {"default": _engine(), "full_record": _engine(PB_EST_LEAN=0), "every_launch": _engine(PB_POLY_ALWAYS=0),
-            "dt_global": _engine(PB_DT_ROWS_REG=0), "dt_rows_wave": _engine(PB_DT_ROWS_REG=2), "dt_rows_regw": _engine(PB_DT_ROWS_REG=3), "dt_cols_sweeps": _engine(PB_DT_COLS_STRIP=0, PB_DT_COLS_COOP=0), "dt_cols_reread": _engine(PB_DT_COLS_STRIP=2, PB_DT_COLS_COOP=0), "dt_cols_threads": _engine(PB_DT_COLS_COOP=0), "dt_cols_coop": _engine(PB_DT_COLS_COOP=2), "taper_three_steps": _engine(PB_POLY_PADDED=0), "taper_full_blends": _engine(PB_TAPER_RING=0), "direct_three_steps": _engine(PB_ZERO_RING=0), "direct_ring": _engine(PB_ZERO_RING_MIN_PAIRS=1)}
+            **{name: _engine(**knobs) for name, knobs in dt_cases.DT_ENGINE_KNOBS.items()},       # dt_global, dt_rows_*, dt_cols_*
+            "taper_three_steps": _engine(PB_POLY_PADDED=0), "taper_full_blends": _engine(PB_TAPER_RING=0), "direct_three_steps": _engine(PB_ZERO_RING=0), "direct_ring": _engine(PB_ZERO_RING_MIN_PAIRS=1)}
 
 
 KW = dict(c=0.362, b=0.468, alpha=6.0, beta=1.0)
@@ -107,22 +110,51 @@ def test_wide_rank1_kernels_take_one_pass_too(engines):
     assert np.abs(out - out2).max() < 5e-6                                              # (another form: rounding only)
 
 
-@pytest.mark.parametrize("shape", [(2, 3, 37, 203), (1, 3, 90, 1920), (1, 1, 33, 1024), (3, 3, 5, 2048), (1, 3, 17, 64), (2, 1, 9, 2),
-                                   (1, 3, 21, 3840), (2, 3, 3, 4096), (1, 1, 7, 2500), (1, 3, 4, 4100), (1, 3, 3, 7680), (1, 1, 2, 8192),
-                                   (2, 3, 5, 257), (1, 3, 6, 1025), (1, 1, 4, 8200)])
-@pytest.mark.parametrize("dtype", [np.float32, np.float16])
+def _dt_choice(eng, name, shape, dtype, self_guided=1):
+    """what csrc/dt_choice.h chooses for this call under the knobs the engine `name` was built with (pb_debug_dt_choice, host only):
+    (row form of the first iteration, chunks, column form, strip / block rows, carry floats, weight floats, LDS)"""
+    import ctypes
+    B, C, H, W = shape
+    out = (ctypes.c_longlong * 7)()
+    assert eng.lib.pb_debug_dt_choice(np.dtype(dtype).itemsize, C, B, H, W, self_guided, 1, (ctypes.c_int * 3)(*dt_cases.knobs_of(name)), out) == 0
+    return tuple(out)
+
+
+# the form each engine is named for: (index into the choice, the values that are that form) -- dt_choice.h's enums
+DT_NAMED_FORM = {"dt_global": (0, (0,)), "dt_rows_wave": (0, (1,)), "dt_rows_regw": (0, (2,)), "dt_cols_sweeps": (2, (0,)),
+                 "dt_cols_reread": (2, (1,)), "dt_cols_threads": (2, (1, 2)), "dt_cols_coop": (2, (3,))}
+
+
+@pytest.mark.parametrize("form", list(dt_cases.DT_ENGINE_KNOBS))
+def test_dt_forced_forms_are_taken(engines, form):
+    """a forced form that does not apply falls back to another one, and a bit-identity test of it would compare the reference with
+    itself: for every dt_* engine at least one shape of the test that names it -- in each of its dtypes for the row forms --
+    takes the form the engine is named for, and the reference engines take nothing but theirs"""
+    field, values = DT_NAMED_FORM[form]
+    rows = form in dt_cases.ROW_FORMS
+    calls = [(s, d) for s in dt_cases.ROW_FORM_SHAPES for d in dt_cases.ROW_FORM_DTYPES] if rows else dt_cases.COLUMN_FORM_CASES
+    took = [(s, np.dtype(d).name) for s, d in calls if _dt_choice(engines[form], form, s, d)[field] in values]
+    if form in ("dt_global", "dt_cols_sweeps"):
+        assert len(took) == len(calls), sorted(set((s, np.dtype(d).name) for s, d in calls) - set(took))
+    for d in {np.dtype(d).name for _, d in calls}:
+        assert [t for t in took if t[1] == d], (form, d)
+
+
+@pytest.mark.parametrize("shape", dt_cases.ROW_FORM_SHAPES)
+@pytest.mark.parametrize("dtype", dt_cases.ROW_FORM_DTYPES)
 def test_dt_rows_register_form(engines, shape, dtype):
-    """the domain transform's row pass with the row in registers (csrc/filters.hip) against the pass through global memory
+    """the domain transform's row pass with the row in registers (csrc/dt.hip) against the pass through global memory
     (domain_transform.py:56-85) -- the same bits -- and the oracle: one wave per row (dt_rows_reg_kernel: rows of up to 1024, 2048,
     4096 samples) and a row over the four waves of a workgroup (dt_rows_regw_kernel: what few rows get; up to 8192 samples) --
-    ragged tails, exactly-full chunks, the widest rows each form takes and one sample beyond, two-sample rows; fp32 and fp16"""
+    ragged tails, exactly-full chunks, the widest rows each form takes and one sample beyond, two-sample rows; fp32 and fp16
+    (tests/dt_form_cases.py; tests/test_dt_choice_cpu.py: every instantiation of both kernels is reached by one of them)"""
     rng = np.random.default_rng(23)
     x = rng.random(shape, dtype=np.float32).astype(dtype)
     want = engines["dt_global"].dt_recursive_filter(x, 2.0, 0.8, 1)
     want3 = engines["dt_global"].dt_recursive_filter(x, 6.0, 0.4, 3)                    # (later iterations: the in-place pass)
     tol = 5e-6 if dtype == np.float32 else 1e-3
     assert np.abs(want.astype(np.float32) - ref.recursive_filter(x.astype(np.float32), 2.0, 0.8, 1)).max() < tol
-    for form in ("default", "dt_rows_wave", "dt_rows_regw"):
+    for form in dt_cases.ROW_FORMS[1:]:
         assert np.array_equal(want, engines[form].dt_recursive_filter(x, 2.0, 0.8, 1)), form
         assert np.array_equal(want3, engines[form].dt_recursive_filter(x, 6.0, 0.4, 3)), form
 
@@ -290,15 +322,12 @@ def test_stage_order_does_not_depend_on_the_batch(engines, shape, dtype, images,
                 assert np.array_equal(np.asarray(infos[k][f])[i], np.asarray(oinfos[k][f])[0]), (i, k, f)
 
 
-DT_COLUMN_FORMS = ("default", "dt_cols_threads", "dt_cols_reread", "dt_cols_coop")
+DT_COLUMN_FORMS = dt_cases.COLUMN_FORMS[1:]                 # ("default", "dt_cols_threads", "dt_cols_reread", "dt_cols_coop")
 
 
-@pytest.mark.parametrize("shape,dtype", [((1, 3, 720, 1280), np.float32), ((2, 3, 203, 333), np.float16), ((1, 1, 1081, 700), np.float32),
-                                         ((3, 3, 64, 97), np.float32), ((1, 3, 65, 40), np.float16), ((1, 1, 1600, 2100), np.float32),
-                                         ((2, 3, 128, 70), np.float32), ((1, 3, 161, 300), np.float32), ((2, 3, 203, 336), np.float16),
-                                         ((1, 3, 31, 64), np.float32), ((2, 1, 96, 136), np.float16)])
+@pytest.mark.parametrize("shape,dtype", dt_cases.COLUMN_FORM_CASES)
 def test_dt_columns_in_strips(engines, shape, dtype):
-    """the column pass of the domain transform (domain_transform.py:56-85) in its forms (csrc/filters.hip) against the two sweeps
+    """the column pass of the domain transform (domain_transform.py:56-85) in its forms (csrc/dt.hip) against the two sweeps
     through global memory -- the same bits -- and the oracle:
     * one thread per column, the down sweep's values formed again strip by strip from one carry per strip: dt_cols_down_kernel,
       then dt_cols_up_kernel with the weights formed again from J over 16 rows, or -- three fp32 channels, 128 rows and up --
