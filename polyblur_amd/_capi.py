@@ -182,5 +182,15 @@ def load_library():
         for name in SYMBOLS:
             fn = getattr(lib, name)           # AttributeError if the library does not export it
             fn.restype, fn.argtypes = proto[name]
+        # the host-only queries of the dispatch layers (api.hip; no device, no context): not part of the product's interface
+        ip = C.POINTER(ci)
+        queries = {
+            "pb_debug_line_choice": (ci, [ci, ci, ci, ci, ip, ip]),
+            "pb_debug_dt_choice": (ci, [ci, ci, ci, ci, ci, ci, ci, ip, C.POINTER(C.c_longlong)]),
+            "pb_debug_poly_plan": (ci, [ci, ip, ci, ip, ci]),
+        }
+        for name, (res, args) in queries.items():
+            if hasattr(lib, name):
+                getattr(lib, name).restype, getattr(lib, name).argtypes = res, args
         _lib = lib
         return lib

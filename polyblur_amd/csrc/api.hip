@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "poly_choice.h"
 
 // (g_dtype: the type of the gradient planes gx, gy, ox -- PB_F32, or PB_F16 inside an fp16 call of the pipeline)
 int pb_grad_energy(pb_ctx *ctx, const void *gx, const void *gy, float *nM, int P, long HW, int g_dtype = PB_F32);
@@ -149,6 +150,25 @@ extern "C" int pb_debug_dt_choice(int elem, int C, int B, int H, int W, int self
     const long long v[7] = {c.rows, c.chunks, c.cols, c.cols_rows, c.carry, c.weights, c.lds};
     std::copy(v, v + 7, out);
     return PB_OK;
+}
+
+// What a reblurring call would issue (poly_choice.h); host only, no device and no context needed.  polynomial: 1 = choose_poly (the
+// three Horner steps), 0 = choose_pass (one pass, step 0 of the per-step facts).  facts: PolyFacts as PB_POLY_NFACTS ints, in the
+// order of the struct.  out: up to max_ops ops of 8 ints each -- kind, step, poly, ring, side stream, known selections, spectra
+// set, arg (PolyOp).  Returns the number of ops, or PB_ERR_BADARG (a plan longer than max_ops or than PB_POLY_MAX_OPS included).
+extern "C" int pb_debug_poly_plan(int polynomial, const int *facts, int n_facts, int *out, int max_ops) {
+    if (!facts || n_facts != PB_POLY_NFACTS || !out || max_ops < 0) return PB_ERR_BADARG;
+    PolyFacts f;
+    memcpy(&f, facts, sizeof(f));
+    if (f.ring < 0 || f.ring > 5 || f.poly < 0 || f.poly > 2) return PB_ERR_BADARG;
+    const PolyPlan pl = polynomial ? choose_poly(f) : choose_pass(f);
+    if (pl.overflow || pl.n > max_ops) return PB_ERR_BADARG;
+    for (int i = 0; i < pl.n; ++i) {
+        const PolyOp &o = pl.op[i];
+        const int v[PB_POLY_OP_INTS] = {o.kind, o.step, o.poly, o.ring, o.side, o.known, o.set, o.arg};
+        std::copy(v, v + PB_POLY_OP_INTS, out + i * PB_POLY_OP_INTS);
+    }
+    return pl.n;
 }
 
 extern "C" {

@@ -306,11 +306,11 @@ int pb_launch_conv_fft(pb_ctx *ctx, const ConvPass &p);
 int pb_launch_conv_strip(pb_ctx *ctx, const ConvPass &p);                    // conv_strip.hip; PB_ERR_UNSUPPORTED: not an all-fp32 plain Horner pass
 // spec: the PolySpec p.khat was built under (Spectra.spec).  known: the records' selections where the host has read them -- the job
 // grid is then exactly this launch's jobs --, nullptr where it has not: the grid is the longest list the spec admits
-int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known);   // conv_wfft.hip; PB_ERR_UNSUPPORTED: dtype combination not built
+int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known);   // conv_wfft.hip; a pass it is not built for is refused (ask pb_conv_wfft_types / _feasible first)
 bool pb_conv_fft_types(const ConvPass &p);                                   // conv_fft.hip: whether the workgroup form is built for the pass's types
 bool pb_conv_wfft_types(const ConvPass &p);
 int pb_launch_conv_w128(pb_ctx *ctx, const ConvPass &p, const std::vector<pb_fft_sel> *known);   // conv_w128.hip: the one-pass polynomial on 128 x 128 windows (pb_fft_sel.poly == 2)
-int pb_launch_conv_win(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known);   // conv_win.hip: the one window pass of every image, 128 x 128 or 64-wide windows by its record, in ONE launch; PB_ERR_UNSUPPORTED: types not built
+int pb_launch_conv_win(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known);   // conv_win.hip: the one window pass of every image, 128 x 128 or 64-wide windows by its record, in ONE launch
 bool pb_conv_win_types(const ConvPass &p);                                   // ... whether it is built for this composite pass
 bool pb_conv_w128_feasible(const ConvPass &p);                               // ... and whether its worst-case job list fits the grid
 bool pb_conv_wfft_feasible(const ConvPass &p, bool poly2);                   // conv_wfft.hip: likewise for the wave form

@@ -25,6 +25,7 @@
 #include "common.h"
 #include "conv_common.h"
 #include "conv_tile_common.h"
+#include "poly_choice.h"
 
 namespace {
 
@@ -324,11 +325,12 @@ int launch_typed(pb_ctx *ctx, const ConvPass &p) {
 // One launch per pass: each image's record decides on the device which body evaluates its tiles, so a batch
 // may mix rank-1 and general kernels and the host never has to read the estimates back.
 static int launch_stencil(pb_ctx *ctx, const ConvPass &p);
-static int launch_tile_spectrum(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known);
 
 // Dense kernels above the context's phase threshold take the tile-spectrum body: a second launch of the same step, in
 // which -- as in the first -- every image's tiles exit at once unless the image's record selects that body.  For record
-// sets the host built and read back itself (rec_cache) the launch no image needs is not issued at all.
+// sets the host built and read back itself (rec_cache) the launch no image needs is not issued at all.  Which launches a
+// pass or a polynomial issues, in which order and on which stream, is one plan per call: poly_choice.h chooses it from the
+// facts gathered below, issue_plan runs it.
 // What the tile-spectrum body needs of a pass: planes within its 32-bit byte offsets, window counts within its index
 // arithmetic.
 static bool fft_pass_ok(const ConvPass &p) {
@@ -355,67 +357,6 @@ static pb_ctx::BodyFlags flags_of(const std::vector<pb_fft_sel> &h) {
         else { f.any_other = true; if (e.strip) f.any_strip = true; else f.any_tile = true; }
     }
     return f;
-}
-
-int pb_launch_conv(pb_ctx *ctx, const ConvPass &p0, const PassWant &want) {
-    ConvPass p = p0;
-    bool fft = ctx->fft_min_phases >= 0 && !p.no_fft && fft_pass_ok(p);
-    const int B = p.P / p.C;
-    const std::vector<pb_fft_sel> *ksel = nullptr;
-    const pb_ctx::BodyFlags *kf = known_flags(ctx, p.info, B, want, &ksel);
-    const bool have = kf != nullptr;
-    // (a step of a polynomial whose one-pass images another launch does: only the images that go step by step count)
-    if (fft && have && !(want.spec.on && p.poly == 0 ? kf->any_fft3 : kf->any_fft)) fft = false;
-    p.fsel = nullptr; p.khat = nullptr;
-    Spectra sp;
-    if (fft || (have && want.spec.on)) {
-        // (spectra an earlier pass built count only while the scratch still holds them for these records)
-        const bool built = (p.khat_ready || have || ctx->spectra.by_estimate()) && ctx->spectra.holds(p.info, B);   // (pb_build_khat also rebuilds spectra of another PolySpec)
-        const int rc = pb_build_khat(ctx, p.info, B, want, !built, &sp);
-        if (rc) return rc;
-        p.khat = sp.khat; p.fsel = sp.sel;      // (the stencil bodies read the selection too: they skip the one-pass images)
-    } else if (!p.khat_ready && !have) {
-        ctx->spectra.drop();     // device-built records took a pass without spectra: whatever the scratch holds is not theirs
-    }
-    // rank-1 kernels of full support on fp32 planes: the streaming strip body (host-built records only: with device-built
-    // ones it would be one more launch that usually finds no work)
-    const bool strip = ctx->strip_mode && have && kf->any_strip && p.in_dtype == PB_F32 && p.x_dtype == PB_F32 &&
-                       p.out_dtype == PB_F32 && p.epilogue == EPI_HORNER && p.pad == PB_KRAD && !p.skip_sep;
-    bool strip_done = false;
-#ifdef PB_EXPERIMENTAL      // (python -m polyblur_amd.build --experimental: conv_strip.hip is a measured experiment, NOTEBOOK.md)
-    if (strip) {
-        p.strip = 1;
-        const int rc = pb_launch_conv_strip(ctx, p);
-        if (rc == PB_OK) strip_done = true;
-        else if (rc != PB_ERR_UNSUPPORTED) return rc;
-        else p.strip = 0;
-    }
-#else
-    (void)strip;
-#endif
-    // (PolySpec.always == 2, records of the estimation: every image takes the window form -- no stencil launch to find that out)
-    const bool windows_only = !have && fft && !want.spec.on && want.spec.always == 2 && ctx->fft_wave && pb_conv_wfft_types(p) &&
-                              pb_conv_wfft_feasible(p, false);
-    const bool tile_needed = windows_only ? false : (!have || (strip_done ? kf->any_tile : kf->any_other));
-    if (tile_needed) {
-        const int rc = launch_stencil(ctx, p);
-        if (rc) return rc;
-    }
-    if (!fft) return PB_OK;
-    return launch_tile_spectrum(ctx, p, sp.spec, ksel);
-}
-
-// the tile-spectrum launch of a pass: the wave form where it is built and worth it, else the workgroup form -- which cannot
-// run one-pass images whose composite halo is beyond its classes (PolySpec.on == 2 is only asked for where the wave form
-// takes every launch, pb_poly_spec).  spec: what p.khat was built under; known: the records where the host has read them
-static int launch_tile_spectrum(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known) {
-    if (ctx->fft_wave) {
-        const int rc = pb_launch_conv_wfft(ctx, p, spec, known);
-        if (rc != PB_ERR_UNSUPPORTED) return rc;
-    }
-    if (p.poly != 0 && spec.on >= 2)
-        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "one-pass polynomial with per-axis halos: the wave form does not take this pass");
-    return pb_launch_conv_fft(ctx, p);
 }
 
 // Which one-pass form a polynomial with these steps may ask for (PolySpec.on): 2 = the composite filter's own halos, where
@@ -477,51 +418,138 @@ static ConvPass composite_pass(const ConvPass *steps) {
     return pc;
 }
 
-// The context's side stream inside one polynomial.  Construction forks it behind what the caller's stream holds so far
-// (`forked`: whether that worked); run() issues a callable's launches on it and records where they end; join() makes the
-// caller's stream wait for that point -- on every way out once the fork has happened: later calls share the scratch planes.
+// ---- the launchers: learn, gather, choose (poly_choice.h), issue ---------------------------------------------------------------
+
+static void gather_step(PolyFacts &f, int s, const ConvPass &p) {
+    f.step_ok[s] = fft_pass_ok(p); f.wave_types[s] = pb_conv_wfft_types(p); f.wave_fits[s] = pb_conv_wfft_feasible(p, false);
+    f.wg_types[s] = pb_conv_fft_types(p);
+    f.strip_pass[s] = p.in_dtype == PB_F32 && p.x_dtype == PB_F32 && p.out_dtype == PB_F32 && p.epilogue == EPI_HORNER && p.pad == PB_KRAD && !p.skip_sep;
+}
+// The knobs, the spec, what the host has read of the B records at `info` under it (*ksel: their selections) and what the first
+// scratch set holds for them -- everything but the passes
+static void gather_call(PolyFacts &f, pb_ctx *ctx, const void *info, int B, const PassWant &want, const std::vector<pb_fft_sel> **ksel) {
+    f.fft_on = ctx->fft_min_phases >= 0; f.fft_wave = ctx->fft_wave; f.poly_one_launch = ctx->poly_one_launch; f.strip_mode = ctx->strip_mode;
+    f.aux = ctx->aux != nullptr; f.prof_on = ctx->prof_on;
+    f.on = want.spec.on; f.always = want.spec.always;
+    if (const pb_ctx::BodyFlags *kf = known_flags(ctx, info, B, want, ksel)) {
+        f.have = 1; f.any_fft = kf->any_fft; f.any_other = kf->any_other; f.any_strip = kf->any_strip; f.any_tile = kf->any_tile; f.any_fft3 = kf->any_fft3;
+        f.ksel = *ksel != nullptr;
+    }
+    // (records the estimation has just built bring their spectra with them: blur_params_kernel ends with them)
+    f.held = ctx->spectra.holds(info, B); f.by_estimate = f.held && ctx->spectra.by_estimate();
+    const bool first = ctx->spectra.holds(info, B, want.spec);
+    f.spectra = !first && want.spec.on != 0 && ctx->spectra2.holds(info, B, want.spec) ? PB_SPECTRA_SECOND
+              : first && ctx->spectra.slot() == want.slot % PB_SEL_SLOTS ? PB_SPECTRA_READY : PB_SPECTRA_STALE;
+}
+
+// The context's side stream inside one plan.  fork() puts it behind what the caller's stream holds so far; use() makes it (or the
+// caller's stream again) the one launches go to, and on the way back records where its launches end; join() makes the caller's
+// stream wait for that point -- on every way out once the fork has happened: later calls share the scratch planes.
 struct SideStream {
     pb_ctx *ctx;
     hipStream_t main;
-    hipError_t forked, recorded = hipErrorNotReady;
-    explicit SideStream(pb_ctx *c) : ctx(c), main(c->stream) {
-        forked = hipEventRecord(ctx->ev_fork, main);
-        if (forked == hipSuccess) forked = hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0);
+    bool forked = false, on_side = false;
+    hipError_t recorded = hipErrorNotReady;
+    explicit SideStream(pb_ctx *c) : ctx(c), main(c->stream) {}
+    hipError_t fork() {
+        hipError_t e = hipEventRecord(ctx->ev_fork, main);
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0);
+        forked = e == hipSuccess;
+        return e;
     }
-    template <typename F> int run(F &&launches) {
-        ctx->stream = ctx->aux;
-        const int rc = launches();
-        ctx->stream = main;
-        recorded = hipEventRecord(ctx->ev_join, ctx->aux);       // (before the caller's stream gets its own launches, as ever)
-        return rc;
+    void use(bool side) {
+        if (side == on_side) return;
+        on_side = side;
+        ctx->stream = side ? ctx->aux : main;
+        if (!side) recorded = hipEventRecord(ctx->ev_join, ctx->aux);       // (before the caller's stream gets its own launches, as ever)
     }
     hipError_t join() {
+        use(false);
+        forked = false;
         return recorded != hipSuccess ? recorded : hipStreamWaitEvent(main, ctx->ev_join, 0);      // (a failed record skips the wait)
     }
 };
 
-// The three Horner steps of one polynomial.  Whether the tile-spectrum body may be used is decided ONCE, from all three
-// geometries (a body decided per step could meet spectra no earlier step had built); its spectra are built by the first
-// step.  One launch sequence per step.
-//
-// Records built on the device (the pipeline) leave the host ignorant of which body an image takes, so every step issues
-// both kernels and, for the usual all-dense or all-separable batch, one of them finds no work: three launches of a few
-// thousand workgroups that leave at once, 6 us each on the critical path.  The two kernels of a step touch different
-// images, so the stencil bodies' three launches go to the context's side stream -- forked behind the spectra, joined
-// before the call returns -- and run (or evaporate) beside the tile-spectrum launches instead of between them.
-int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps, const PassWant &want) {
-    const PolySpec &spec = want.spec;
-    bool fft = ctx->fft_min_phases >= 0;
-    for (int s = 0; s < 3; ++s) fft = fft && fft_pass_ok(steps[s]);
+// Issues a plan.  steps: the pass, or the three Horner steps with `whole`, their composite pass (ConvPass.poly = 1); ksel: the
+// records' selections where the host has read them.
+static int issue_plan(pb_ctx *ctx, const PolyPlan &pl, const ConvPass *steps, const ConvPass *whole, const PassWant &want,
+                      const std::vector<pb_fft_sel> *ksel) {
+    if (pl.overflow) return pb_fail(ctx, PB_ERR_BADARG, "conv pass: a plan of more than %d launches", PB_POLY_MAX_OPS);
+    if (pl.failed()) {
+        const PolyOp &o = pl.op[pl.n - 1];
+        const ConvPass &p = o.step == PB_PASS_WHOLE ? *whole : steps[o.step];
+        return pb_fail(ctx, PB_ERR_UNSUPPORTED, PB_POLY_MSG[o.arg], p.in_dtype * 9 + p.x_dtype * 3 + p.out_dtype);
+    }
     const pb_blur_info *info = steps[0].info;
     const int B = steps[0].P / steps[0].C;
+    Spectra sp, ring;
+    SideStream side(ctx);
+    int strip_step = -1;        // the step whose rank-1 images of full support the strip body has taken
+    int rc = PB_OK;
+    for (int i = 0; i < pl.n && !rc; ++i) {
+        const PolyOp &o = pl.op[i];
+        side.use(o.side != 0);
+        ConvPass p = o.step == PB_PASS_WHOLE ? *whole : steps[o.step];
+        const Spectra &s = o.set == PB_SET_RING ? ring : sp;
+        p.khat = o.set ? s.khat : nullptr; p.fsel = o.set ? s.sel : nullptr;      // (the stencil bodies read the selection too: they skip the one-pass images)
+        p.poly = o.poly; p.ring = o.ring; p.strip = strip_step == o.step;
+        if (o.poly == 2 && whole) {       // the first step's launch takes the one-pass images along: for them it is the composite pass
+            p.out2 = whole->out; p.out2_kind = whole->out_kind; p.out2_pitch = whole->out_pitch; p.out2_plane = whole->out_plane;
+            p.clamp2 = whole->clamp01;
+        }
+        const std::vector<pb_fft_sel> *known = o.known ? ksel : nullptr;
+        switch (o.kind) {
+            case PB_OP_BUILD: rc = pb_build_khat(ctx, info, B, want, o.arg != 0, &sp); break;
+            case PB_OP_BUILD_RING: rc = pb_build_khat_ring(ctx, info, B, want, &ring); break;
+            case PB_OP_DROP: ctx->spectra.drop(); break;      // whatever the scratch holds is not these records'
+            case PB_OP_STENCIL: if (o.arg != PB_WHEN_STRIP_REFUSED || !p.strip) rc = launch_stencil(ctx, p); break;
+            case PB_OP_WAVE: rc = pb_launch_conv_wfft(ctx, p, s.spec, known); break;
+            case PB_OP_WG: rc = pb_launch_conv_fft(ctx, p); break;
+            case PB_OP_W128: rc = pb_launch_conv_w128(ctx, p, known); break;
+            case PB_OP_WIN: rc = pb_launch_conv_win(ctx, p, s.spec, known); break;
+#ifdef PB_EXPERIMENTAL      // (python -m polyblur_amd.build --experimental: conv_strip.hip is a measured experiment, NOTEBOOK.md)
+            case PB_OP_STRIP:
+                p.strip = 1;
+                rc = pb_launch_conv_strip(ctx, p);
+                if (rc == PB_OK) strip_step = o.step;
+                else if (rc == PB_ERR_UNSUPPORTED) rc = PB_OK;      // not this pass: the tile body keeps it
+                break;
+#endif
+            case PB_OP_FORK: { const hipError_t e = side.fork(); if (e != hipSuccess) rc = pb_fail(ctx, PB_ERR_HIP, "side stream: fork failed: %s", hipGetErrorString(e)); break; }
+            case PB_OP_JOIN: { const hipError_t e = side.join(); if (e != hipSuccess) rc = pb_fail(ctx, PB_ERR_HIP, "side stream: join failed: %s", hipGetErrorString(e)); break; }
+            default: break;
+        }
+    }
+    if (side.forked) {
+        const hipError_t e = side.join();
+        if (e != hipSuccess) return pb_fail(ctx, PB_ERR_HIP, "side stream: join failed: %s", hipGetErrorString(e));
+    }
+    return rc;
+}
+
+int pb_launch_conv(pb_ctx *ctx, const ConvPass &p, const PassWant &want) {
+    const std::vector<pb_fft_sel> *ksel = nullptr;
+    PolyFacts f = {};
+    gather_call(f, ctx, p.info, p.P / p.C, want, &ksel);
+    gather_step(f, 0, p);
+    f.no_fft = p.no_fft; f.khat_ready = p.khat_ready; f.ring = p.ring; f.poly = p.poly;
+    return issue_plan(ctx, choose_pass(f), &p, nullptr, want, ksel);
+}
+
+// The three Horner steps of one polynomial (poly_choice.h: choose_poly has the forms).
+int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps, const PassWant &want) {
+    const PolySpec &spec = want.spec;
+    const pb_blur_info *info = steps[0].info;
+    const int B = steps[0].P / steps[0].C;
+    PolyFacts f = {};
+    for (int s = 0; s < 3; ++s) gather_step(f, s, steps[s]);
     // Records the host built (pb_make_kernels / pb_set_kernels) meeting a one-pass spec for the first time: the spectra of
     // that spec are built and the device's choice read back now -- one synchronisation per record set and spec -- so that
     // every later polynomial on them issues exactly the launches it needs, with job grids of exactly the size it needs.
     {
         const auto known = ctx->rec_cache.find(info);
-        if (fft && spec.on && known != ctx->rec_cache.end() && known->second.B == B &&
-            !(known->second.poly_valid && same_spec(known->second.spec, spec))) {
+        if (ctx->fft_min_phases >= 0 && f.step_ok[0] && f.step_ok[1] && f.step_ok[2] && spec.on && known != ctx->rec_cache.end() &&
+            known->second.B == B && !(known->second.poly_valid && same_spec(known->second.spec, spec))) {
             Spectra s0;
             int rc0 = pb_build_khat(ctx, info, B, want, true, &s0);
             if (rc0) return rc0;
@@ -532,184 +560,16 @@ int pb_launch_conv_poly(pb_ctx *ctx, const ConvPass *steps, const PassWant &want
             rf.poly_valid = true; rf.spec = spec; rf.poly = flags_of(h); rf.sel = h;
         }
     }
-    // (what the host has read of these records under the spec: their flags, and their selections -- ksel -- for exact job grids)
     const std::vector<pb_fft_sel> *ksel = nullptr;
-    const pb_ctx::BodyFlags *kf = known_flags(ctx, info, B, want, &ksel);
-    const bool have = kf != nullptr;
-    // (records the estimation has just built bring their spectra with them: blur_params_kernel ends with them)
-    const bool held = ctx->spectra.holds(info, B), by_estimate = held && ctx->spectra.by_estimate();
-    // (per-launch profiling keeps everything on one stream: events on the side stream would time its launches' wait
-    // behind the other kernel's workgroups, not their work)
-    // One-pass polynomial: the images whose spectrum is the polynomial's take ONE window pass from the first step's input
-    // to the last step's output; the later steps' launches skip them.  When the first and the last step store the same
-    // type, the first step's launch takes them along (ConvPass.poly = 2: no launch of their own, nothing to pay when no
-    // image qualifies); otherwise a composite launch does them.  (The spectra the steps meet are those `want.spec`
-    // asks for: pb_build_khat rebuilds any others.)
-    // PolySpec.always == 2 (records of the estimation): every image on three window steps, three launches of the wave body
-    if (fft && !spec.on && spec.always == 2 && !have) {
-        Spectra sp;
-        int rc = pb_build_khat(ctx, info, B, want, !by_estimate, &sp);
-        for (int s = 0; s < 3 && !rc; ++s) {
-            ConvPass p = steps[s];
-            p.khat = sp.khat; p.fsel = sp.sel; p.poly = 0;
-            rc = pb_launch_conv_wfft(ctx, p, sp.spec, nullptr);
-            if (rc == PB_ERR_UNSUPPORTED) rc = pb_fail(ctx, PB_ERR_UNSUPPORTED, "three window steps: the wave form does not take this pass");
-        }
-        return rc;
-    }
-    const bool poly_on = fft && spec.on;
-    const bool fold = poly_on && steps[0].out_dtype == steps[2].out_dtype;
+    gather_call(f, ctx, info, B, want, &ksel);
     const ConvPass whole = composite_pass(steps);
-    auto with_spectra = [](ConvPass p, const Spectra &sp) { p.khat = sp.khat; p.fsel = sp.sel; return p; };
-    auto first_step = [&](ConvPass &p) {
-        if (!fold) return;
-        p.poly = 2;
-        p.out2 = whole.out; p.out2_kind = whole.out_kind; p.out2_pitch = whole.out_pitch; p.out2_plane = whole.out_plane;
-        p.clamp2 = whole.clamp01;
-    };
-    // (the composite launch sizes its grid for the longest job list the spectra's spec admits, whatever the host has read)
-    auto composite = [&](const Spectra &sp) -> int {
-        const ConvPass pc = with_spectra(whole, sp);
-        if (!fft_pass_ok(pc)) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "one-pass polynomial: composite pass not feasible");
-        return launch_tile_spectrum(ctx, pc, sp.spec, nullptr);
-    };
-    // the images whose one pass runs on 128 x 128 windows (pb_fft_sel.poly == 2): a launch of their own, beside the others
-    auto composite128 = [&](const Spectra &sp) -> int {
-        if (spec.on != 3) return PB_OK;
-        return pb_launch_conv_w128(ctx, with_spectra(whole, sp), ksel);
-    };
-    // The side stream pays where the launches that may find no work are expensive -- one workgroup per 64 x 64 tile of every
-    // plane: 6 us at 4K, 33 us for 32 x 1080p -- against two queue-to-queue waits per polynomial (~5 - 8 us each); a single
-    // image of up to 4K runs everything on the caller's stream (measured: 4K 0.738 -> 0.722 ms of device time per call, while
-    // 32 x 1080p would go from 6.09 to 6.61 ms without the side stream).
-    // PolySpec.always (records of the estimation, nothing the host has read back): every image takes one window pass, on 64 x 64
-    // or on 128 x 128 windows -- one launch on the caller's stream whose workgroups run either body (two launches, each skipping
-    // the other's images, before conv_win.hip: the empty one cost a 4K call 3.5 - 5.8 us per iteration), and nothing else.
-    if (poly_on && spec.always && !have) {
-        Spectra sp;
-        int rc = pb_build_khat(ctx, info, B, want, !by_estimate, &sp);
-        if (rc) return rc;
-        auto window_pass = [&]() -> int {
-            // one launch carries both window forms (conv_win.hip) where it is built for the composite's types; PB_POLY_ONE_LAUNCH=0,
-            // or types it is not built for: the two launches, each skipping the other's images
-            if (ctx->poly_one_launch && ctx->fft_wave && spec.on == 3) {
-                const ConvPass pc = with_spectra(whole, sp);
-                if (pb_conv_win_types(pc)) {
-                    if (!fft_pass_ok(pc)) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "one-pass polynomial: composite pass not feasible");
-                    return pb_launch_conv_win(ctx, pc, sp.spec, nullptr);
-                }
-            }
-            const int e = composite128(sp);
-            if (e) return e;
-            if (pb_conv_wfft_types(whole)) return composite(sp);
-            ConvPass p = with_spectra(steps[0], sp);         // (the composite's types are not built: the first step's launch takes them along)
-            first_step(p);
-            return launch_tile_spectrum(ctx, p, sp.spec, nullptr);
-        };
-        if (steps[0].boundary != PB_ZERO) return window_pass();
-        // The zero boundary: the window pass is the polynomial of the zero-EXTENDED image, which is the three-step result
-        // (every step truncated to the padded domain, filters.py:40-49) everywhere but within 24 samples of the padded border
-        // -- 12 of the image's.  That frame is recomputed by three Horner steps over the ring of window pairs it depends on
-        // (conv_wfft.hip: ring_live; the kernels' own spectra in a second scratch set), the last of which overwrites the
-        // frame's tiles of the output.  A ring step is a race of single window pairs (one or two rounds of ~20 us whatever
-        // its size), so the first two -- which touch neither the output nor the first set of spectra -- run on the side
-        // stream BESIDE the window pass; only the third waits for both.
-        Spectra ring;
-        auto ring_steps = [&](int s0, int s1) -> int {
-            int e = PB_OK;
-            for (int s = s0; s < s1 && !e; ++s) {
-                ConvPass p = with_spectra(steps[s], ring);
-                p.ring = s + 1; p.poly = 0;
-                e = pb_launch_conv_wfft(ctx, p, ring.spec, nullptr);
-                if (e == PB_ERR_UNSUPPORTED) e = pb_fail(ctx, PB_ERR_UNSUPPORTED, "zero-boundary ring: the wave form does not take this pass");
-            }
-            return e;
-        };
-        auto first_two = [&]() -> int {
-            const int e = pb_build_khat_ring(ctx, info, B, want, &ring);
-            return e ? e : ring_steps(0, 2);
-        };
-        if (ctx->aux && !ctx->prof_on) {
-            SideStream side(ctx);
-            PB_HIP(side.forked);
-            const int rc_side = side.run(first_two);
-            rc = window_pass();
-            PB_HIP(side.join());
-            if (!rc) rc = rc_side;
-        } else {
-            rc = window_pass();
-            if (!rc) rc = first_two();
-        }
-        return rc ? rc : ring_steps(2, 3);
-    }
-    // Lab switch of tools/one_launch_timing.py (PB_POLY_ONE_LAUNCH=2): host-built records whose every image takes one window pass
-    // go through the merged launch too, with the exact grid -- what the pipeline's launch costs, without the estimation around it.
-    if (poly_on && have && ctx->poly_one_launch == 2 && ctx->fft_wave && spec.on == 3 && steps[0].boundary != PB_ZERO) {
-        if (ksel && kf->any_fft && !kf->any_other && !kf->any_fft3 && pb_conv_win_types(whole)) {
-            Spectra sp;
-            const int rc = pb_build_khat(ctx, info, B, want, !held, &sp);
-            if (rc) return rc;
-            const ConvPass pc = with_spectra(whole, sp);
-            if (!fft_pass_ok(pc)) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "one-pass polynomial: composite pass not feasible");
-            return pb_launch_conv_win(ctx, pc, sp.spec, ksel);
-        }
-    }
-    constexpr long min_side_tiles = 12288;      // (a 4K image has 6405 stencil tiles, 32 x 1080p 53568)
-    const long stencil_tiles = (long)((steps[0].H + 2 * steps[0].pad + 63) / 64) * ((steps[0].W + 2 * steps[0].pad + 63) / 64) * steps[0].P;
-    const bool side_pays = ctx->aux && stencil_tiles >= min_side_tiles;
-    if (!fft || have || !side_pays || ctx->prof_on) {
-        if (fft && spec.on == 3) {
-            Spectra sp;
-            int rc = pb_build_khat(ctx, info, B, want, !(held && (have || by_estimate)), &sp);
-            if (rc) return rc;
-            rc = composite128(sp);
-            if (rc) return rc;
-        }
-        for (int s = 0; s < 3; ++s) {
-            ConvPass p = steps[s];
-            p.khat_ready = s > 0;
-            if (!fft) p.no_fft = 1;
-            if (s == 0) first_step(p);
-            const int rc = pb_launch_conv(ctx, p, want);
-            if (rc) return rc;
-        }
-        if (poly_on && !fold) {
-            // (the spectra the three steps have just used -- the first set's, or the second's behind an edgetaper -- and the spec they
-            // were built under: images with a one-pass record wait for this launch)
-            Spectra sp;
-            const int rc = pb_build_khat(ctx, info, B, want, false, &sp);
-            return rc ? rc : composite(sp);
-        }
-        return PB_OK;
-    }
-    Spectra sp;
-    int rc = pb_build_khat(ctx, info, B, want, !by_estimate, &sp);
-    if (rc) return rc;
-    // Which launches stay on the caller's stream: those that probably do the work -- crossing to the side stream and back
-    // costs two queue-to-queue waits (~5 us each) on the critical path.  Where the spec admits 128 x 128 windows that is the
-    // 128 x 128 launch, and the wave body's three launches join the stencil launches on the side stream; otherwise the wave body's.
-    const bool w128_main = poly_on && spec.on == 3;
-    auto wave_steps = [&]() -> int {
-        int e = PB_OK;
-        for (int s = 0; s < 3 && !e; ++s) {
-            ConvPass p = with_spectra(steps[s], sp);
-            if (s == 0) first_step(p);
-            e = launch_tile_spectrum(ctx, p, sp.spec, nullptr);
-        }
-        return e;
-    };
-    SideStream side(ctx);
-    PB_HIP(side.forked);
-    rc = side.run([&]() -> int {
-        // (the composite pass touches other images than the steps' launches do: it, too, runs -- or finds no work -- beside them)
-        int e = poly_on && !fold ? composite(sp) : PB_OK;
-        if (w128_main && !e) e = wave_steps();
-        for (int s = 0; s < 3 && !e; ++s) e = launch_stencil(ctx, with_spectra(steps[s], sp));
-        return e;
-    });
-    if (!rc) rc = w128_main ? composite128(sp) : wave_steps();
-    PB_HIP(side.join());
-    return rc;
+    f.whole_ok = fft_pass_ok(whole); f.whole_wave_types = pb_conv_wfft_types(whole); f.whole_wave_fits = pb_conv_wfft_feasible(whole, false);
+    f.whole_wg_types = pb_conv_fft_types(whole); f.whole_win_types = pb_conv_win_types(whole);
+    f.zero = steps[0].boundary == PB_ZERO;
+    f.fold = steps[0].out_dtype == steps[2].out_dtype;
+    // (one workgroup per 64 x 64 tile of every plane: a 4K image has 6405 stencil tiles, 32 x 1080p 53568)
+    f.side_tiles = (long)((steps[0].H + 2 * steps[0].pad + 63) / 64) * ((steps[0].W + 2 * steps[0].pad + 63) / 64) * steps[0].P >= PB_POLY_MIN_SIDE_TILES;
+    return issue_plan(ctx, choose_poly(f), steps, &whole, want, ksel);
 }
 
 // The host has just (re)built these B records and is synchronising anyway: build their spectra, read the per-image choice

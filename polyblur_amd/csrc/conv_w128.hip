@@ -164,6 +164,6 @@ int pb_launch_conv_w128(pb_ctx *ctx, const ConvPass &p, const std::vector<pb_fft
         case 6: return launch_w128_typed<unsigned char, float>(ctx, p, g, groups);
         case 7: return launch_w128_typed<unsigned char, __half>(ctx, p, g, groups);
         case 8: return launch_w128_typed<unsigned char, unsigned char>(ctx, p, g, groups);
-        default: return PB_ERR_UNSUPPORTED;
+        default: return pb_fail(ctx, PB_ERR_UNSUPPORTED, "128 x 128 window pass: unsupported dtype combination %d -> %d", p.in_dtype, p.out_dtype);
     }
 }

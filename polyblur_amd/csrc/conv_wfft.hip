@@ -167,23 +167,23 @@ bool pb_conv_wfft_types(const ConvPass &p) {
     }
 }
 
-// PB_ERR_UNSUPPORTED: dtype combination not built (the caller falls back to the workgroup form).  Every pass whose types
-// are built comes here whatever its size, so that what an image gets does not depend on the batch it travels in (the two
+// A pass it is not built for -- a dtype combination without a kernel, a three-step job list beyond the grid -- is refused: the
+// chooser (poly_choice.h) asks pb_conv_wfft_types / pb_conv_wfft_feasible first and plans the workgroup form there.  Every pass whose
+// types are built comes here whatever its size, so that what an image gets does not depend on the batch it travels in (the two
 // forms round differently: this one rotates the window rows and has per-axis halos).  A wave takes ~19 us for its pair
 // whatever the size of the launch, a 512-thread workgroup ~8 us, so a three-step pass of a few hundred pairs is a race of
 // single pairs that the workgroup form used to win (700 x 500: 0.31 against 0.38 ms per call); with small images' polynomials
 // mostly one window pass now, the call is faster through this form alone (0.29 ms; 1080p 0.45 against 0.53).
 int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known) {
-    if (!pb_conv_wfft_types(p)) return PB_ERR_UNSUPPORTED;
+    const int key = p.in_dtype * 9 + p.x_dtype * 3 + p.out_dtype;
+    if (!pb_conv_wfft_types(p)) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "wave-form pass: unsupported dtype combination %d", key);
     const bool poly2 = p.poly != 0 && spec.on >= 2;
     const float min_area = (float)PB_POLY_MIN_AREA;        // (the smallest one-pass tile the cost model of khat.h admits)
     WGeom g;
     long per_max = 0;
     const bool tall = poly2 && spec.tall != 0;
-    if (!wfft_geometry(p, poly2, tall, min_area, g, per_max)) {
-        if (poly2) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "conv pass: too many windows for the tile-spectrum body");
-        return PB_ERR_UNSUPPORTED;
-    }
+    if (!wfft_geometry(p, poly2, tall, min_area, g, per_max))
+        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "conv pass: too many windows for the tile-spectrum body");
     long groups = 8L * per_max * p.P;                       // list entries if every image had the smallest tiles its records may select
     if (known) {
         // the host has the records' choices (it built them): the grid is exactly the list of this launch's jobs
@@ -202,7 +202,7 @@ int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, co
     ProfScope prof(ctx, PB_PROF_CONV_FFT);
     // fp32 planes; the second and third Horner step of fp16 images (fp32 temporaries in, fp16 x operand, fp32 or fp16 out);
     // the first step and the one-pass polynomial of fp16 images (fp16 window)
-    switch (p.in_dtype * 9 + p.x_dtype * 3 + p.out_dtype) {
+    switch (key) {
         case 0: return launch_wfft_typed<float, float, float>(ctx, p, g, groups);
         case 1: return launch_wfft_typed<float, float, __half>(ctx, p, g, groups);          // (the last store of an fp16 image after fp32 iterations)
         case 3: return launch_wfft_typed<float, __half, float>(ctx, p, g, groups);
@@ -216,6 +216,6 @@ int pb_launch_conv_wfft(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, co
         case 6: return launch_wfft_typed<float, unsigned char, float>(ctx, p, g, groups);
         case 8: return launch_wfft_typed<float, unsigned char, unsigned char>(ctx, p, g, groups);
         case 2: return launch_wfft_typed<float, float, unsigned char>(ctx, p, g, groups);
-        default: return PB_ERR_UNSUPPORTED;
+        default: return pb_fail(ctx, PB_ERR_UNSUPPORTED, "wave-form pass: unsupported dtype combination %d", key);
     }
 }

@@ -157,9 +157,9 @@ bool pb_conv_win_types(const ConvPass &p) {
 // The one window pass of every image of the batch, whichever form its record selects (p: the composite pass).  The grid is the
 // longer of the two forms' worst-case job lists where the host has not read the records, else (`known`: the timing tool's
 // lab switch) exactly the images' lists.  spec: what p.khat was built under (behind an edgetaper: the second set's).
-// PB_ERR_UNSUPPORTED: types not built -- the caller issues the two launches.
+// A pass pb_conv_win_types does not admit is refused: the chooser (poly_choice.h) asks first and plans the two launches there.
 int pb_launch_conv_win(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, const std::vector<pb_fft_sel> *known) {
-    if (!pb_conv_win_types(p)) return PB_ERR_UNSUPPORTED;
+    if (!pb_conv_win_types(p)) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "one-launch window pass: not built for this pass (types %d -> %d)", p.in_dtype, p.out_dtype);
     const bool poly2 = spec.on >= 2, tall = poly2 && spec.tall != 0;
     WGeom g;
     long per_max = 0;
@@ -189,6 +189,6 @@ int pb_launch_conv_win(pb_ctx *ctx, const ConvPass &p, const PolySpec &spec, con
         case 4: return launch_win_typed<__half, __half>(ctx, p, g, groups);
         case 6: return launch_win_typed<unsigned char, float>(ctx, p, g, groups);
         case 8: return launch_win_typed<unsigned char, unsigned char>(ctx, p, g, groups);
-        default: return PB_ERR_UNSUPPORTED;
+        default: return pb_fail(ctx, PB_ERR_UNSUPPORTED, "one-launch window pass: not built for this pass (types %d -> %d)", p.in_dtype, p.out_dtype);
     }
 }
