@@ -418,6 +418,22 @@ int pb_halo_mask_backward(pb_ctx *ctx, const float *x, const float *y, const flo
 int pb_dt_recursive_filter(pb_ctx *ctx, const void *in, const void *joint, void *out, int dtype,
                            int B, int C, int H, int W, float sigma_s, float sigma_r, int num_iterations);
 
+/* pb_dt_recursive_filter_backward: the backward of pb_dt_recursive_filter (domain_transform.py:6-85 under autograd) with respect to
+ * the image and to the guide; no gradient with respect to the two sigma.  in, joint, grad_out (the upstream gradient of out),
+ * grad_in and grad_joint are (B,C,H,W) float32 DEVICE memory.  joint == NULL: the filter is guided by `in`; grad_joint must then be
+ * NULL and grad_in receives both paths.  Either output may be NULL (not both), and what a NULL output makes unnecessary is not
+ * computed: without a guide gradient neither the planes of the weights' adjoint nor the guide kernel.  Outputs are written, not
+ * accumulated; they alias no input and do not alias each other.  A NULL context, non-positive sizes, a sigma that is not positive
+ * and finite or num_iterations < 1: PB_ERR_BADARG before any launch.  The 2 N passes are run again keeping the input of each
+ * (the forward saves nothing; the filter's only kink, |J[i] - J[i-1]|, is decided by the inputs, so nothing depends on the
+ * forward's bits), then each pass backward: two sweeps per line that form f with P and g with Q (csrc/stage_math.h).  Scratch:
+ * 2 N + 2 plane sets -- "dtg.x" (2 N - 1 of them: the inputs of passes 1 .. 2 N - 1), "dtg.f", "dtg.p", "dtg.g" -- and, with a guide
+ * gradient, two (B,H,W) planes ("dtg.dx", "dtg.dy").  fp32 sums in an order the shape alone fixes, no float atomics: the same call
+ * gives the same bits.  Timed under PB_PROF_PREFILTER.  Asynchronous on the context's stream.                                  */
+int pb_dt_recursive_filter_backward(pb_ctx *ctx, const float *in, const float *joint, const float *grad_out,
+                                    float *grad_in, float *grad_joint,
+                                    int B, int C, int H, int W, float sigma_s, float sigma_r, int num_iterations);
+
 /* normalized_convolution (NC.cpp:143-204), the domain-transform variant built on box filters in the
  * transformed domain; single-image semantics of the reference applied per image, any C.  H, W <= 8190. */
 int pb_dt_normalized_convolution(pb_ctx *ctx, const void *in, void *out, int dtype, int B, int C, int H, int W,

@@ -14,7 +14,8 @@ from .nonblind import compute_polynomial, inverse_filtering_nonsymmetric  # noqa
 from .estimation import gaussian_blur_estimation  # noqa: F401
 # halo masking and the spectral derivative, differentiable (reference deblurring.py:193-208, filters.py:159-186)
 from .halo import fourier_gradients, halo_masking  # noqa: F401
-# the edge-aware filters behind prefiltering=True; the bilateral filter is differentiable, the other two are forward only
+# the edge-aware filters behind prefiltering=True; the bilateral filter and the recursive filter (image and guide) are
+# differentiable, the normalized convolution is forward only
 # (reference filters.py:107-148, domain_transform.py:6-85, deblurring.py:99-110)
 from .edge_aware import bilateral_filter, recursive_filter, normalized_convolution, edge_aware_filtering  # noqa: F401
 

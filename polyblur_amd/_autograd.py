@@ -1,4 +1,4 @@
-"""The package's autograd.Functions (DESIGN.md 4.7-4.9, 4.12): the forward and backward passes are the engine's, on ROCm float32
+"""The package's autograd.Functions (DESIGN.md 4.7-4.9, 4.12, 4.13): the forward and backward passes are the engine's, on ROCm float32
 tensors and torch's current stream; no double backward.  The public functions import this module on first use under grad --
 it is the only one that needs torch at import time -- after every check and refusal of theirs has passed."""
 from __future__ import annotations
@@ -149,6 +149,34 @@ class HaloMaskingFunction(torch.autograd.Function):
             eng.halo_mask_backward_ptr(x.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), g.data_ptr(),
                                        *[o.data_ptr() if o is not None else None for o in outs], x.shape)
         return tuple(outs) + (None,)
+
+
+class RecursiveFilterFunction(torch.autograd.Function):
+    """recursive_filter of ROCm float32 tensors, differentiated with respect to the image and to joint_image (None: guided by the
+    image, whose gradient then holds both paths); the two sigma and the iteration count are Python numbers.
+    filt: (image, joint or None, sigma_s, sigma_r, n) -> the filtered image (edge_aware._recursive)"""
+
+    @staticmethod
+    def forward(ctx, img, joint, sigma_s, sigma_r, num_iterations, filt):
+        x = img.detach().contiguous()
+        j = None if joint is None else joint.detach().contiguous()
+        out = filt(x, j, sigma_s, sigma_r, num_iterations)
+        ctx.save_for_backward(*((x,) if j is None else (x, j)))
+        ctx.pb = (float(sigma_s), float(sigma_r), int(num_iterations))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, j = (ctx.saved_tensors + (None,))[:2]
+        g = _upstream(grad_out)
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gj = torch.empty_like(j) if j is not None and ctx.needs_input_grad[1] else None
+        with bound_engine(x) as eng:
+            eng.dt_recursive_filter_backward_ptr(x.data_ptr(), None if j is None else j.data_ptr(), g.data_ptr(),
+                                                 None if gx is None else gx.data_ptr(), None if gj is None else gj.data_ptr(),
+                                                 x.shape, *ctx.pb)
+        return gx, gj, None, None, None, None
 
 
 class BilateralFunction(torch.autograd.Function):

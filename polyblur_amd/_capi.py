@@ -42,6 +42,7 @@ SYMBOLS = [
     "pb_compute_polynomial_taps", "pb_inverse_filter_phase_taps", "pb_set_phase_budget",
     "pb_tap_gradient", "pb_convolve2d_taps_backward", "pb_compute_polynomial_taps_backward", "pb_estimate_blur_backward",
     "pb_fourier_gradients_backward", "pb_halo_mask_backward", "pb_bilateral_backward",
+    "pb_dt_recursive_filter_backward",
     "pb_comm_shard", "pb_comm_unique_id", "pb_comm_init", "pb_comm_destroy", "pb_comm_scatter", "pb_comm_gather",
     "pb_comm_deblur_from_root", "pb_comm_plan_steps", "pb_comm_plan", "pb_comm_set_chunk", "pb_comm_default_chunk",
     "pb_comm_plan_steps_chunked", "pb_comm_plan_chunked",
@@ -153,6 +154,7 @@ def load_library():
             "pb_fourier_gradients_backward": (ci, [vp, vp, vp, ci, ci, ci, vp]),
             "pb_halo_mask_backward": (ci, [vp] * 10 + [ci, ci, ci, ci]),
             "pb_dt_recursive_filter": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, ci]),
+            "pb_dt_recursive_filter_backward": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, ci]),
             "pb_dt_normalized_convolution": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, ci]),
             "pb_bilateral5": (ci, [vp, vp, vp, ci, ci, ci, ci, ci]),
             "pb_bilateral": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, cf]),

@@ -917,13 +917,6 @@ __global__ __launch_bounds__(NT) void dt_cols_coop_kernel(const TJ *__restrict__
     if (wave > 0) store_rows(0);
 }
 
-// the filter's coefficient of iteration i of N (domain_transform.py:50,53), as the logarithm the kernels take
-float dt_log_a(float sigma_s, int i, int N) {
-    const double sigma_i = (double)sigma_s * std::sqrt(3.0) * std::pow(2.0, N - (i + 1)) / std::sqrt(std::pow(4.0, N) - 1.0);
-    const float a = (float)std::exp(-std::sqrt(2.0) / sigma_i);
-    return std::log(a);
-}
-
 // One or three channels: what choose_dt chose for the call -- asked once, its scratch requested once, the cooperative kernel's
 // LDS limit raised once -- then per iteration a row pass (the chosen form in the first, in place through global memory
 // afterwards) and a column pass.

@@ -88,6 +88,39 @@ __device__ __forceinline__ PbHalo pb_halo_ratio(float gx, float gy, float ox, fl
 }
 
 // ------------------------------------------------------------------------------------
+// domain transform: the recursive filter and its backward (dt.hip, dt_grad.hip)
+// ------------------------------------------------------------------------------------
+// A call is 2 N one-dimensional passes, rows then columns for iteration k = 0 .. N - 1 (domain_transform.py:48-61), with
+// a_k = exp(log_a_k), log_a_k = dt_log_a(sigma_s, k, N).  One pass along a line of n samples: input x (C channels), weights
+// v_i = exp(d_i log_a_k) shared by the channels, d_i = 1 + ratio sum_c |J_c,i - J_c,i-1| for i >= 1, ratio = sigma_s / sigma_r.
+//
+//   forward   f_0 = x_0;            f_i = x_i + v_i (f_{i-1} - x_i)          i = 1 .. n-1
+//             g_{n-1} = f_{n-1};    g_i = f_i + v_{i+1} (g_{i+1} - f_i)      i = n-2 .. 0
+//   backward, given G (the adjoint of the pass's output g)
+//             P_0 = G_0;            P_i = G_i + v_i P_{i-1}                  left -> right
+//             fbar_i = (1 - v_{i+1}) P_i  (i < n-1);   fbar_{n-1} = P_{n-1}
+//             Q_{n-1} = fbar_{n-1}; Q_i = fbar_i + v_{i+1} Q_{i+1}           right -> left
+//             xbar_i = (1 - v_i) Q_i  (i >= 1);        xbar_0 = Q_0
+//             vbar_i = sum_c P_{i-1} (g_i - f_{i-1}) + Q_i (f_{i-1} - x_i)   i >= 1
+//   weights   Dbar_i = sum_k log_a_k v_{k,i} vbar_{k,i}      one plane for the rows (Dbar_x), one for the columns (Dbar_y)
+//   guide     Jbar_c,i = ratio (s_c,i Dbar_i - s_c,i+1 Dbar_{i+1}),  s_c,i = sign(J_c,i - J_c,i-1),  sign(0) = 0; the terms
+//             with i = 0 and with i + 1 = n are absent; the row term and the column term add
+//
+// xbar of a pass is G of the pass before it; xbar of the first pass is the gradient of the image (plus Jbar when the filter is
+// guided by its own input).  The only kink, |J_i - J_{i-1}|, is a function of the inputs: the backward forms f, g and v again
+// with its own arithmetic and owes nothing to the forward's bits.
+
+// the filter's coefficient of iteration i of N (domain_transform.py:50,53), as the logarithm the kernels take
+inline float dt_log_a(float sigma_s, int i, int N) {
+    const double sigma_i = (double)sigma_s * std::sqrt(3.0) * std::pow(2.0, N - (i + 1)) / std::sqrt(std::pow(4.0, N) - 1.0);
+    const float a = (float)std::exp(-std::sqrt(2.0) / sigma_i);
+    return std::log(a);
+}
+// v = a^d from l1 = sum_c |J_c,i - J_c,i-1|, and the factor of that sum's derivative with respect to J_c,i
+__device__ __forceinline__ float pb_dt_weight(float l1, float ratio, float log_a) { return expf((1.f + ratio * l1) * log_a); }
+__device__ __forceinline__ float pb_dt_sign(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
+
+// ------------------------------------------------------------------------------------
 // sums and extrema in a fixed order (no float atomics: the same call gives the same bits)
 // ------------------------------------------------------------------------------------
 // over the 64 lanes of a wave by xor shuffles: every lane gets the result

@@ -16,9 +16,16 @@ weights one sample off its taps, filters.py:109 against utils.pad_with_kernel).
 Gradients: with autograd on and ``I`` a float32 ROCm tensor that requires grad, ``bilateral_filter`` returns a
 tensor with a ``grad_fn`` -- the same bits as under ``torch.no_grad()``; the backward pass is the engine's
 (pb_bilateral_backward), with respect to the image, no double backward -- and ``edge_aware_filtering(prefilter='bilateral')``
-returns ``(img_smoothed, img - img_smoothed)``, both in the graph.  Every other operand that requires grad -- a CPU or float16
-tensor, ``recursive_filter``, ``normalized_convolution``, the other two values of ``prefilter``, a ``joint_image`` -- is refused
-before any device work; under ``torch.no_grad()`` the call runs.
+returns ``(img_smoothed, img - img_smoothed)``, both in the graph.  ``recursive_filter`` is differentiable with
+respect to ``I`` and to ``joint_image``: when either requires grad and both are float32 ROCm tensors on one device it returns a
+tensor with a ``grad_fn`` -- again the bits of ``torch.no_grad()``; the backward pass is the engine's
+(pb_dt_recursive_filter_backward), a gradient for each operand that asks for one (guided by itself, ``I.grad`` holds both
+paths), none with respect to ``sigma_s`` / ``sigma_r``, no double backward.  Every other operand that requires grad -- a CPU or
+float16 tensor, an array beside a tensor that requires grad, operands on two devices, ``normalized_convolution``, the other two
+values of ``prefilter`` -- is refused before any device work; under ``torch.no_grad()`` the call runs.
+``edge_aware_filtering(prefilter='domain_transform')`` and ``polyblur_deblurring(prefiltering=True,
+prefilter='domain_transform')`` are still refused under grad (the follow-up); until then compose
+``smooth = recursive_filter(x, sigma_s, sigma_r, 1); noise = x - smooth``.
 
 The filters are the HIP engine's (pb_bilateral, pb_dt_recursive_filter, pb_dt_normalized_convolution); ``img_noise`` is the
 subtraction ``img - img_smoothed`` in the image's own kind, as the reference writes it.
@@ -30,7 +37,7 @@ import math
 import numpy as np
 
 from . import _capi as capi
-from ._frontend import _PREFILTER, DTYPES, check_image, is_rocm_float32, refuse_under_grad, staged, wants_grad
+from ._frontend import _PREFILTER, DTYPES, check_image, is_rocm_float32, is_tensor, refuse_under_grad, staged, wants_grad
 
 _NO_GRAD = "the edge-aware filters are not differentiated"
 _NC_MAX_SIDE = 8190                                # pb_dt_normalized_convolution: H, W <= 8190
@@ -81,12 +88,37 @@ def bilateral_filter(I, ksize=5, sigma_spatial=5.0, sigma_color=0.1):
     return _bilateral(I, int(ksize), ss, sc, dt)
 
 
+def _recursive(I, joint_image, ss, sr, n, dt=np.dtype(np.float32)):
+    """the one call of pb_dt_recursive_filter: the public function's forward, and RecursiveFilterFunction's"""
+    shape = tuple(I.shape)
+    extra = () if joint_image is None else (("np.joint", joint_image, dt.type),)
+    return staged(I, dt, lambda eng, i, o, ex: eng.dt_recursive_filter_ptr(i, ex[0] if ex else None, o[0], DTYPES[dt], shape, ss, sr, n),
+                  extra)[0][0]
+
+
+def _describe(t):
+    if not is_tensor(t):
+        return type(t).__module__.split(".")[0] + "." + type(t).__name__
+    return "%s tensor on %s" % (str(t.dtype).replace("torch.", ""), t.device)
+
+
+def _recursive_grad_refusal(I, joint_image):
+    """why ``recursive_filter`` cannot differentiate these operands, or None: both must be float32 ROCm tensors on one device"""
+    operands = [I] if joint_image is None else [I, joint_image]
+    if all(is_rocm_float32(t) for t in operands) and len({t.device for t in operands}) == 1:
+        return None
+    if not any(is_tensor(t) and t.is_cuda for t in operands):
+        return _NO_GRAD                                # (no ROCm tensor in the call: the refusal it has always had)
+    return ("gradients are built for float32 ROCm tensors on one device, I and joint_image alike (got I: %s%s)"
+            % (_describe(I), "" if joint_image is None else ", joint_image: %s" % _describe(joint_image)))
+
+
 def recursive_filter(I, sigma_s=60, sigma_r=0.4, num_iterations=3, joint_image=None):
     """domain_transform.recursive_filter (domain_transform.py:6-85): the domain-transform recursive filter, guided by
-    ``joint_image`` (an image of ``I``'s shape, read in ``I``'s dtype) or by ``I`` itself."""
+    ``joint_image`` (an image of ``I``'s shape, read in ``I``'s dtype) or by ``I`` itself.  Differentiable with respect to ``I``
+    and ``joint_image`` when they are float32 ROCm tensors on one device and either requires grad (the module docstring)."""
     shape, dt = check_image(I, allow_half=True)
     ss, sr, n = _positive("sigma_s", sigma_s), _positive("sigma_r", sigma_r), _iterations(num_iterations)
-    extra = ()
     if joint_image is not None:
         try:
             jshape, _ = check_image(joint_image, allow_half=True)
@@ -96,11 +128,13 @@ def recursive_filter(I, sigma_s=60, sigma_r=0.4, num_iterations=3, joint_image=N
             jshape = None
         if jshape != shape:
             raise ValueError("joint_image must have the image's shape %r, got %r" % (shape, tuple(joint_image.shape)))
-        extra = (("np.joint", joint_image, dt.type),)
     if wants_grad(I, joint_image):
-        refuse_under_grad("recursive_filter", _NO_GRAD)
-    return staged(I, dt, lambda eng, i, o, ex: eng.dt_recursive_filter_ptr(i, ex[0] if ex else None, o[0], DTYPES[dt], shape, ss, sr, n),
-                  extra)[0][0]
+        reason = _recursive_grad_refusal(I, joint_image)
+        if reason is not None:
+            refuse_under_grad("recursive_filter", reason)
+        from ._autograd import RecursiveFilterFunction
+        return RecursiveFilterFunction.apply(I, joint_image, ss, sr, n, _recursive)
+    return _recursive(I, joint_image, ss, sr, n, dt)
 
 
 def normalized_convolution(I, sigma_s=60, sigma_r=0.4, num_iterations=3):

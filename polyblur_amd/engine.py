@@ -433,6 +433,15 @@ class Engine:
         self._check(self.lib.pb_dt_recursive_filter(self.ctx, in_ptr, joint_ptr, out_ptr, int(dtype), B, Cc, H, W, float(sigma_s),
                                                     float(sigma_r), int(num_iterations)))
 
+    def dt_recursive_filter_backward_ptr(self, in_ptr: int, joint_ptr, grad_out_ptr: int, grad_in_ptr, grad_joint_ptr, shape,
+                                         sigma_s, sigma_r, num_iterations):
+        """d loss / d image and d loss / d guide of dt_recursive_filter_ptr's filter, float32 (pb_dt_recursive_filter_backward).
+        joint_ptr None: guided by the input -- grad_joint_ptr must be None, grad_in receives both paths; either output may be None
+        (not both) and is then not computed; the outputs alias no input and not each other; asynchronous"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_dt_recursive_filter_backward(self.ctx, in_ptr, joint_ptr, grad_out_ptr, grad_in_ptr, grad_joint_ptr,
+                                                             B, Cc, H, W, float(sigma_s), float(sigma_r), int(num_iterations)))
+
     def dt_normalized_convolution_ptr(self, in_ptr: int, out_ptr: int, dtype: int, shape, sigma_s, sigma_r, num_iterations):
         """pb_dt_normalized_convolution (H, W <= 8190); asynchronous"""
         B, Cc, H, W = (int(v) for v in shape)
