@@ -359,13 +359,29 @@ int pb_convolve2d_taps_backward(pb_ctx *ctx, const float *x, const float *grad_o
                                 int B, int C, int H, int W, const pb_taps *taps, int boundary);
 
 /* Backward of pb_compute_polynomial_taps with not_symmetric == 0 (deblurring.compute_polynomial, deblurring.py:113-169;
- * the pure-phase variant has no backward).  With g = grad_out, g2 = K^T g, g1 = K^T g2:
+ * the pure-phase variant: pb_compute_polynomial_phase_taps_backward).  With g = grad_out, g2 = K^T g, g1 = K^T g2:
  *   grad_x = b g + a1 g2 + a2 g1 + a3 K^T g1 -- the same polynomial of K^T, in whichever form the forward would take;
  *   grad_taps (device, (B,kh,kw)) = L(g, t2) + L(g2, t1) + L(g1, a3 x) with the forward's temporaries t1, t2 formed again by
  *   explicit Horner steps (context scratch: four plane sets of the domain, "grad.t1" .. "grad.g1", and the partial tables).
  * NULL rules as above.  The argument rules and refusals of pb_compute_polynomial_taps.                                        */
 int pb_compute_polynomial_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps,
                                         int B, int C, int H, int W, const pb_taps *taps, float alpha, float beta, int boundary);
+
+/* Backward of pb_compute_polynomial_taps with not_symmetric != 0 (deblurring.compute_polynomial_fft with the pure-phase filter,
+ * deblurring.py:141-169; p2o: filters.py:255-273).  H x W is the whole circular domain.  With K = fft2(p2o(kernel)), r = |K|,
+ * C = conj(K) / (r + 1e-8), P the polynomial of K, P' its derivative, M = C P, N = H W, g = grad_out:
+ *   grad_x = Re ifft2(conj(M) fft2(g)) -- the forward's passes with the conjugate multiplier;
+ *   grad_taps (device, (B,kh,kw))[i][j] = Re fft2(S) at ((i - kh/2) mod H, (j - kw/2) mod W) -- the adjoint of p2o, a gather --,
+ *   S = A (C_K P + C P') + conj(A C_Kbar P), A = (1 / N) sum over the image's planes of fft2(x) conj(fft2(g)),
+ *   C_K = -conj(K)^2 / (2 r (r + eps)^2), C_Kbar = 1 / (r + eps) - r / (2 (r + eps)^2): C is a function of K and of conj(K).
+ * Kernel sides even or odd, as the forward takes them.  grad_x or grad_taps may be NULL (then not computed, and no bit of the other
+ * changes), not both; x may be NULL when grad_taps is.  Outputs are written, not accumulated, and alias neither an input nor each
+ * other (PB_ERR_BADARG, before any launch).  PB_ERR_UNSUPPORTED before any launch where a side has pb_fft_length_supported != 1.
+ * Scratch: complex H x W planes "phaseg.k", "phaseg.g" (one per plane pair of a group) and, with grad_taps, "phaseg.x" (as many)
+ * and "phaseg.a"; groups as pb_set_phase_budget sizes them, two planes a pair with grad_taps.  fp32 sums in an order the shape
+ * alone fixes, no float atomics: the same call gives the same bits, whatever the budget.                                     */
+int pb_compute_polynomial_phase_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps,
+                                              int B, int C, int H, int W, const pb_taps *taps, float alpha, float b);
 
 /* ---- gradient of the blind estimation.  The README's promise covers the headline call too: in the reference the kernel that
  * gaussian_blur_estimation returns (blur_estimation.py:18-79) is a differentiable function of the image -- through the tap formula

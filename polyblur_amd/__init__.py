@@ -8,7 +8,8 @@ first call.  There is no CPU fallback: without the library or a GPU the calls ra
 from .deblurring import polyblur_deblurring, polyblur_deblurring_uint8, PolyblurDeblurring  # noqa: F401
 # the non-blind step with a kernel of the caller's (reference deblurring.py:211-239, filters.py:14-37, edgetaper.py:26-33)
 from .nonblind import inverse_filtering_rank3, convolve2d, edgetaper  # noqa: F401
-# ... and for kernels that are not point-symmetric: the pure-phase filter (reference deblurring.py:113-169, not_symmetric=True)
+# ... and for kernels that are not point-symmetric: the pure-phase filter (reference deblurring.py:113-169, not_symmetric=True),
+# differentiable with respect to the image and the kernel like the three above
 from .nonblind import compute_polynomial, inverse_filtering_nonsymmetric  # noqa: F401
 # the blind estimation itself, differentiable (reference blur_estimation.py:18-79)
 from .estimation import gaussian_blur_estimation  # noqa: F401

@@ -1,4 +1,4 @@
-"""The package's autograd.Functions (DESIGN.md 4.7-4.9, 4.12, 4.13): the forward and backward passes are the engine's, on ROCm float32
+"""The package's autograd.Functions (DESIGN.md 4.7-4.9, 4.12-4.14): the forward and backward passes are the engine's, on ROCm float32
 tensors and torch's current stream; no double backward.  The public functions import this module on first use under grad --
 it is the only one that needs torch at import time -- after every check and refusal of theirs has passed."""
 from __future__ import annotations
@@ -22,6 +22,18 @@ def replicate_pad(x, pad):
     B, C, H, W = x.shape
     x = torch.cat([x[:, :, :1].expand(B, C, pad, W), x, x[:, :, -1:].expand(B, C, pad, W)], dim=2)
     return torch.cat([x[..., :1].expand(B, C, H + 2 * pad, pad), x, x[..., -1:].expand(B, C, H + 2 * pad, pad)], dim=3)
+
+
+def _kernel_grad(gk, kernel_like, B, correlate):
+    """the engine's (B', kh, kw) tap gradient back to kernel.shape: the taps were broadcast over the batch (summed here; the engine
+    has summed over the planes of a one-channel kernel) and rotated for correlate=True (rotated back)"""
+    (kb, kc, kh, kw), kdtype, kdevice = kernel_like
+    gk = gk.view(B, kc, kh, kw)
+    if kb == 1 and B > 1:
+        gk = gk.sum(0, keepdim=True)
+    if correlate:
+        gk = gk.flip(-2, -1)
+    return gk.to(device=kdevice, dtype=kdtype)
 
 
 class TapsFunction(torch.autograd.Function):
@@ -62,16 +74,43 @@ class TapsFunction(torch.autograd.Function):
             finally:
                 ks.free()                               # (waits for the stream)
         if want_k:
-            # back to kernel.shape: the taps were broadcast over the batch (summed here; the engine has summed over the
-            # planes of a one-channel kernel) and rotated for correlate=True (rotated back)
-            (kb, kc, kh, kw), kdtype, kdevice = ctx.kernel_like
-            gk = gk.view(B, kc, kh, kw)
-            if kb == 1 and B > 1:
-                gk = gk.sum(0, keepdim=True)
-            if correlate:
-                gk = gk.flip(-2, -1)
-            gk = gk.to(device=kdevice, dtype=kdtype)
+            gk = _kernel_grad(gk, ctx.kernel_like, B, correlate)
         return gx, gk, None, None, None, None, None, None
+
+
+class PhaseFunction(torch.autograd.Function):
+    """compute_polynomial(method='fft', not_symmetric=True) of a ROCm float32 image that is the whole domain; kernel
+    sides even or odd.  The arguments are TapsFunction's, with poly = (alpha, b)."""
+
+    @staticmethod
+    def forward(ctx, img, kernel, taps, eshape, poly, correlate, call):
+        x = img.detach()
+        (out,), _ = staged(x, np.float32, call, taps=taps)
+        ctx.save_for_backward(x)
+        ctx.pb = (taps, poly, bool(correlate), int(img.shape[0]), eshape)
+        ctx.kernel_like = None if kernel is None else (tuple(int(v) for v in kernel.shape), kernel.dtype, kernel.device)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        (x,) = ctx.saved_tensors
+        taps, poly, correlate, B, eshape = ctx.pb
+        want_x, want_k = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        xin = x.contiguous()
+        g = _upstream(grad_out)
+        gx = torch.empty_like(xin) if want_x else None
+        gk = torch.empty(taps.shape, dtype=torch.float32, device=x.device) if want_k else None
+        with bound_engine(x) as eng:
+            ks = eng.set_taps(taps)
+            try:
+                eng.compute_polynomial_phase_taps_backward_ptr(xin.data_ptr(), g.data_ptr(), gx.data_ptr() if want_x else None,
+                                                               gk.data_ptr() if want_k else None, eshape, ks, poly[0], poly[1])
+            finally:
+                ks.free()                               # (waits for the stream)
+        if want_k:
+            gk = _kernel_grad(gk, ctx.kernel_like, B, correlate)
+        return gx, gk, None, None, None, None, None
 
 
 class EstimationFunction(torch.autograd.Function):

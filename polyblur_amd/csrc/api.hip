@@ -1532,4 +1532,26 @@ int pb_compute_polynomial_taps_backward(pb_ctx *ctx, const float *x, const float
     return PB_OK;
 }
 
+int pb_compute_polynomial_phase_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps, int B,
+                                              int C, int H, int W, const pb_taps *taps, float alpha, float beta) {
+    static const char *who = "pb_compute_polynomial_phase_taps_backward";
+    int rc = check_shape(ctx, PB_F32, B, C, H, W);
+    if (rc) return rc;
+    // (backward_args with no set: even sides are taken -- nothing in this adjoint is centred, it is a gather at p2o's positions)
+    rc = backward_args(ctx, who, x, grad_out, grad_x, grad_taps, nullptr);
+    if (rc) return rc;
+    Geometry g; const pb_blur_info *recs = nullptr;
+    rc = taps_geometry(ctx, taps, B, C, H, W, PB_WRAP, true, false, &g, &recs);
+    if (rc) return rc;
+    rc = pb_phase_sides_supported(ctx, H, W);
+    if (rc) return rc;
+    PB_HIP(hipSetDevice(ctx->device));
+    PhaseGradCall c;
+    c.x = x; c.grad_out = grad_out; c.grad_x = grad_x; c.grad_taps = grad_taps;
+    c.B = B; c.C = C; c.H = H; c.W = W;
+    c.taps = taps->raw; c.kh = taps->kh; c.kw = taps->kw;
+    c.alpha = alpha; c.beta = beta;
+    return pb_launch_phase_backward(ctx, c);
+}
+
 }  // extern "C"

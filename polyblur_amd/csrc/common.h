@@ -343,6 +343,15 @@ struct PhaseCall {
 };
 int pb_launch_phase(pb_ctx *ctx, const PhaseCall &c);
 int pb_phase_sides_supported(pb_ctx *ctx, int Hp, int Wp);                   // PB_ERR_UNSUPPORTED (message set) unless both sides' lines fit LDS
+// its backward (conv_phase_grad.hip): x, grad_out, grad_x (B,C,H,W) fp32 planes that are the whole domain, grad_taps (B,kh,kw);
+// grad_x or grad_taps may be null (not computed), not both; x may be null without grad_taps
+struct PhaseGradCall {
+    const float *x, *grad_out; float *grad_x, *grad_taps;
+    int B, C, H, W;
+    const float *taps; int kh, kw;
+    float alpha, beta;
+};
+int pb_launch_phase_backward(pb_ctx *ctx, const PhaseGradCall &c);
 
 // the gradient of a pass with respect to its taps (conv_grad.hip): grad[b][i][j] (= or +=, `accumulate`) scale * the lag
 // correlation of u with v over the C planes of image b -- (B,C,H,W) fp32 planes that are the whole domain, kh and kw odd, v zero

@@ -19,11 +19,10 @@
 #include <algorithm>
 
 #include "common.h"
+#include "conv_phase_common.h"
 #include "fft.h"
 
 namespace {
-
-constexpr size_t kPhaseMaxLds = 160 * 1024;
 
 // where the planes of a call live.  virt: an un-padded H x W plane addressed in padded coordinates (replicate pad by index clamp)
 struct PhaseSrc { const void *p; int virt; int pitch; long plane; };
@@ -35,14 +34,6 @@ __device__ __forceinline__ float phase_ld(const PhaseSrc &src, long plane, int r
         c = min(max(c - pad, 0), W - 1);
     }
     return pb_ld<T>(static_cast<const T *>(src.p) + plane * src.plane + (long)r * src.pitch + c);
-}
-
-// slot `g` of the call: planes 2q and 2q + 1 of image g / spi, the second one missing where C is odd
-__device__ __forceinline__ void phase_slot(int g, int C, long &plane, bool &two) {
-    const int spi = (C + 1) >> 1;
-    const int b = g / spi, q = g - b * spi;
-    plane = (long)b * C + 2 * q;
-    two = 2 * q + 1 < C;
 }
 
 // grid (ceil(Hp / nb), slots): nb rows of one slot, element (c, j) at s[c * nb + j]
@@ -165,39 +156,6 @@ __global__ __launch_bounds__(NTH) void phase_rows_inv(const float2 *__restrict__
         pb_st<T>(out + plane * H * W + (long)r * W + c, x1);
         if (two) pb_st<T>(out + (plane + 1) * H * W + (long)r * W + c, x2);
     }
-}
-
-size_t phase_lds(const FftPlan *pl, int lognb) { return ((size_t)(pl->bluestein_m ? pl->bluestein_m : pl->n) << lognb) * sizeof(float2); }
-
-// rows: a few lines per workgroup while they fit 32 KB (short lines would leave most of a workgroup idle)
-int phase_rows_lognb(const FftPlan *pl, int rows) {
-    int lognb = 3;
-    while (lognb > 0 && (phase_lds(pl, lognb) > 32 * 1024 || (1 << lognb) > 2 * rows)) --lognb;
-    return lognb;
-}
-// columns: the widest tile, up to 16 columns (128 bytes of a complex row), whose lines fit 80 KB -- two workgroups per CU;
-// where not even two lines do (Bluestein cores of 8192), two lines in one workgroup if LDS holds them: 16 contiguous bytes
-// per row instead of 8
-int phase_cols_lognb(const FftPlan *pl, int cols) {
-    int lognb = 4;
-    while (lognb > 0 && (phase_lds(pl, lognb) > 80 * 1024 || (1 << lognb) > 2 * cols)) --lognb;
-    if (lognb == 0 && cols > 1 && phase_lds(pl, 1) <= kPhaseMaxLds) lognb = 1;
-    return lognb;
-}
-// a workgroup's transform is a chain of dependent stages: large LDS footprints leave room for one workgroup per CU, which
-// then runs 1024 threads
-bool phase_wide(size_t lds) { return lds >= 128 * 1024; }
-
-// one launch of the 256- or the 1024-thread instantiation of a kernel, by its LDS footprint
-template <typename K, typename... A>
-int phase_launch(pb_ctx *ctx, K k256, K k1024, dim3 grid, size_t lds, A... args) {
-    const bool wide = phase_wide(lds);
-    K k = wide ? k1024 : k256;
-    if (lds > 48 * 1024)
-        PB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k, grid, dim3(wide ? 1024 : 256), lds, ctx->stream, args...);
-    PB_LAUNCH_CHECK();
-    return PB_OK;
 }
 
 template <typename T>

@@ -32,8 +32,16 @@ are the engine's too (pb_convolve2d_taps_backward, pb_compute_polynomial_taps_ba
 ``inverse_filtering_rank3`` are then torch's own ops -- the replicate pad composed of slices, expand and cat, whose backward is
 an ordered sum where F.pad's adds with float atomics.  ``remove_halo=True`` under grad is ``halo_masking`` (halo.py; DESIGN.md
 4.9) between the crop and the clamp, differentiable with respect to ``grad_img`` too.  Under grad: float32 ROCm tensors and odd
-kernel sides only, and no ``do_edgetaper``, ``edgetaper()``, ``not_symmetric`` or ``inverse_filtering_nonsymmetric``
-(NotImplementedError before any device work).  Without grad nothing changes: the calls below run as before.
+kernel sides only, and no ``do_edgetaper`` or ``edgetaper()`` (NotImplementedError before any device work).  Without grad
+nothing changes: the calls below run as before.
+
+``compute_polynomial(..., not_symmetric=True)`` and ``inverse_filtering_nonsymmetric`` are differentiable in the same way (DESIGN.md
+4.14): the backward of the pure-phase polynomial is the engine's pb_compute_polynomial_phase_taps_backward -- the image gradient
+is the forward's transform with the conjugate multiplier, the tap gradient a gather from one more transform, through the phase
+factor conj(K) / |K| as well --, and ``inverse_filtering_nonsymmetric`` is composed as ``inverse_filtering_rank3`` is.  Kernel
+sides even or odd: nothing in that adjoint is centred.  Under grad: float32 ROCm tensors, no ``do_edgetaper``, padded sides the
+engine holds in LDS.  With no ROCm tensor among the operands the refusal is the one it has always been ("the pure-phase filter is
+not differentiated").
 
 The arithmetic is the HIP engine's (include/polyblur_hip.h: pb_taps_create and the *_taps calls); nothing runs on the CPU.
 """
@@ -94,14 +102,15 @@ def _run(img, dt, taps, call, extra=()):
     return staged(img, dt, call, (("np.g0x", extra[0]), ("np.g0y", extra[1])) if extra else (), taps=taps)[0][0]
 
 
-def _check_grad(img, kernel, what):
-    """what the backward passes are built for -- raised before any device work"""
+def _check_grad(img, kernel, what, even_ok=False):
+    """what the backward passes are built for -- raised before any device work.  even_ok: the pure-phase filter's adjoint is a
+    gather at p2o's positions, nothing in it is centred"""
     if is_tensor(img):
         import torch
         if img.dtype == torch.float16:
             refuse_under_grad(what + " of a float16 image", FLOAT32_ONLY)
     kh, kw = (int(v) for v in kernel.shape[-2:])
-    if kh % 2 == 0 or kw % 2 == 0:
+    if not even_ok and (kh % 2 == 0 or kw % 2 == 0):
         refuse_under_grad(what + " with a %d x %d kernel" % (kh, kw), "the adjoint of an even kernel side sits one sample off centre -- odd sides only")
     for name, t in (("img", img), ("kernel", kernel)):
         if is_tensor(t) and t.requires_grad and not t.is_cuda:
@@ -113,6 +122,17 @@ def _check_grad(img, kernel, what):
 def _apply_taps_function(img, kernel, taps, eshape, bnd, poly, call, correlate=False):
     from ._autograd import TapsFunction
     return TapsFunction.apply(img, kernel if is_tensor(kernel) else None, taps, eshape, bnd, poly, correlate, call)
+
+
+def _any_rocm(*operands):
+    return any(is_tensor(t) and t.is_cuda for t in operands)
+
+
+def _apply_phase_function(img, kernel, taps, eshape, alpha, b, correlate=False):
+    """compute_polynomial(method='fft', not_symmetric=True) of ``img``, the whole domain, inside the graph"""
+    from ._autograd import PhaseFunction
+    call = lambda eng, i, o, ex, ks: eng.compute_polynomial_taps_ptr(i, o[0], eshape, ks, alpha, b, capi.PB_WRAP, True)
+    return PhaseFunction.apply(img, kernel if is_tensor(kernel) else None, taps, eshape, (alpha, b), correlate, call)
 
 
 def convolve2d(img, kernel, method='direct'):
@@ -197,7 +217,8 @@ def compute_polynomial(img, kernel, alpha, b, method='fft', not_symmetric=False)
     """deblurring.compute_polynomial (deblurring.py:113-169): a3 K^3 x + a2 K^2 x + a1 K x + b x on ``img``, which is the whole
     domain (float32; treated as convolve2d treats it); unclamped.  ``not_symmetric=True`` ('fft' only): the pure-phase filter
     conj(K) / (|K| + 1e-8) first -- for a kernel that is not point-symmetric.  Under 'direct' the reference takes the flag and
-    ignores it; here that is a ValueError.  Where |K| falls to fp32 roundoff the filter's phase is noise (see the module)."""
+    ignores it; here that is a ValueError.  Where |K| falls to fp32 roundoff the filter's phase is noise (see the module).
+    Differentiable with respect to ``img`` and ``kernel``, with the flag too (float32 ROCm tensors)."""
     shape, dt = check_image(img, allow_half=False)
     taps, eshape = _check_kernel(kernel, method, shape, pad_domain=False, circular_only=False)
     if not_symmetric and method != "fft":
@@ -206,7 +227,11 @@ def compute_polynomial(img, kernel, alpha, b, method='fft', not_symmetric=False)
     call = lambda eng, i, o, ex, ks: eng.compute_polynomial_taps_ptr(i, o[0], eshape, ks, alpha, b, bnd, bool(not_symmetric))
     if wants_grad(img, kernel):
         if not_symmetric:
-            refuse_under_grad("compute_polynomial(not_symmetric=True)", _NO_PHASE)
+            if not _any_rocm(img, kernel):
+                refuse_under_grad("compute_polynomial(not_symmetric=True)", _NO_PHASE)
+            _check_grad(img, kernel, "compute_polynomial(not_symmetric=True)", even_ok=True)
+            check_phase_sides(shape[2], shape[3])
+            return _apply_phase_function(img, kernel, taps, eshape, alpha, b)
         _check_grad(img, kernel, "compute_polynomial")
         return _apply_taps_function(img, kernel, taps, eshape, bnd, (alpha, b), call)
     if not_symmetric:
@@ -218,13 +243,35 @@ def inverse_filtering_nonsymmetric(img, kernel, alpha=2, b=4, correlate=False, r
                                    grad_img=None):
     """inverse_filtering_rank3's chain (deblurring.py:211-239) with compute_polynomial(method='fft', not_symmetric=True) in the
     polynomial's place: replicate pad by w // 2 -> [edgetaper, 'fft'] -> phase-corrected polynomial -> crop -> [halo masking]
-    -> clamp.  float32 or float16 images.  Where |K| falls to fp32 roundoff the filter's phase is noise (see the module)."""
+    -> clamp.  float32 or float16 images.  Where |K| falls to fp32 roundoff the filter's phase is noise (see the module).
+    Differentiable with respect to ``img``, ``kernel`` and ``grad_img`` (float32 ROCm tensors, no ``do_edgetaper``)."""
     shape, dt = check_image(img, allow_half=True)
     taps, eshape = _check_kernel(kernel, "fft", shape, pad_domain=True, circular_only=bool(do_edgetaper),
                                     correlate=bool(correlate))
-    if wants_grad(img, kernel):
-        refuse_under_grad("inverse_filtering_nonsymmetric", _NO_PHASE)
+    halo_planes = tuple(grad_img) if remove_halo and isinstance(grad_img, (tuple, list)) and len(grad_img) == 2 else ()
     pad = taps.shape[-1] // 2
+    if not _any_rocm(img, kernel, *halo_planes):
+        if wants_grad(img, kernel):
+            refuse_under_grad("inverse_filtering_nonsymmetric", _NO_PHASE)
+    elif wants_grad(img, kernel, *halo_planes):
+        # inverse_filtering_rank3's composition with the phase-corrected polynomial in the polynomial's place
+        if remove_halo and not all(is_rocm_float32(t) for t in (img,) + halo_planes):
+            refuse_under_grad("inverse_filtering_nonsymmetric(remove_halo=True)", HALO_ONLY)
+        if do_edgetaper:
+            refuse_under_grad("inverse_filtering_nonsymmetric(do_edgetaper=True)", NO_EDGETAPER)
+        _check_grad(img, kernel, "inverse_filtering_nonsymmetric", even_ok=True)
+        check_phase_sides(shape[2] + 2 * pad, shape[3] + 2 * pad)
+        if remove_halo:
+            check_image_size(*shape[-2:])
+            if grad_img is not None:
+                check_grad_img(grad_img, shape)
+        from ._autograd import replicate_pad
+        xp = replicate_pad(img, pad)
+        y = _apply_phase_function(xp, kernel, taps, eshape[:2] + tuple(xp.shape[-2:]), alpha, b, bool(correlate))
+        y = y[..., pad:-pad, pad:-pad]
+        if remove_halo:
+            y = halo_masking(img, y, grad_img)                # (grad_img None: fourier_gradients(img), inside the graph)
+        return y.clamp(0.0, 1.0)
     check_phase_sides(shape[2] + 2 * pad, shape[3] + 2 * pad)
     dtype = DTYPES[dt]
     return _chain(img, dt, shape, taps, remove_halo, grad_img,
