@@ -367,6 +367,28 @@ int pb_convolve2d_taps_backward(pb_ctx *ctx, const float *x, const float *grad_o
 int pb_compute_polynomial_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps,
                                         int B, int C, int H, int W, const pb_taps *taps, float alpha, float beta, int boundary);
 
+/* Backward of pb_edgetaper_taps (edgetaper.edgetaper, edgetaper.py:10-33), with respect to the image and to the taps -- the taper
+ * weights A = v1 (x) v2 are functions of the kernel (autocorrelations of its projections, normalised per kernel: the "per-image
+ * maximum" above) and are differentiated too.  With x_0 = x, x_{i+1} = A x_i + (1 - A) (K x_i) and g_n = grad_out, for
+ * i = n - 1 .. 0:  u_i = (1 - A) g_{i+1};  g_i = A g_{i+1} + K^T u_i (the pass with the set's other orientation);
+ * grad_taps += L(u_i, x_i) (pb_tap_gradient's lag correlation);  Abar += sum over the image's planes of g_{i+1} (x_i - K x_i).
+ * grad_x = g_0.  Then once per kernel, per axis (n the side, k the projection, ac its autocorrelation, z[p] = ac[p] + ac[n-1-p]):
+ *   vbar1[py] = sum_px Abar v2[px], vbar2[px] = sum_py Abar v1[py];  zbar[p] = -vbar[p] / ac[0];
+ *   acbar[l] = zbar[l] + zbar[n-1-l], acbar[0] += sum_p vbar[p] z[p] / ac[0]^2;  kbar[m] = sum_l acbar[l] (k[m+l] + k[m-l]);
+ * and grad_taps[b][i][j] += kbar_y[i] + kbar_x[j].  grad_taps: device, (B,kh,kw), in the orientation of the caller's taps.
+ * The taps' placement per boundary is the forward's (convolution under PB_WRAP, correlation under PB_ZERO), through the passes of
+ * pb_convolve2d_taps_backward.  ODD kh and kw, up to 49 (PB_ERR_UNSUPPORTED otherwise); the fit and shape refusals of
+ * pb_edgetaper_taps; n_tapers < 0: PB_ERR_BADARG; B above 65535: PB_ERR_UNSUPPORTED; n_tapers == 0: grad_x = grad_out, grad_taps = 0.  grad_x or grad_taps may be
+ * NULL (then not computed, and no bit of the other changes), not both; grad_out may not be NULL; x may be NULL when grad_taps is --
+ * the image gradient is linear in grad_out and reads only the kernel.  Outputs are written, not accumulated, and alias neither an
+ * input nor each other (PB_ERR_BADARG).  Every refusal comes before any launch.
+ * Scratch, in plane sets of the domain (B*C*H*W floats): "etg.u", "etg.ag" always, "etg.g" when n_tapers > 1 -- three; with grad_taps
+ * also "etg.kx" (K x_i) and "etg.x" (x_1 .. x_{n-1}, formed again by the forward's own blends: n_tapers - 1 sets) -- n_tapers + 3 in
+ * all --, "etg.abar" (B planes), "etg.vbar" (B * (H + W) floats) and pb_tap_gradient's partial tables.  fp32 sums in an order the
+ * shape alone fixes, no float atomics: the same call gives the same bits.  Timed under PB_PROF_OTHER and the passes' own tags.  */
+int pb_edgetaper_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps,
+                               int B, int C, int H, int W, const pb_taps *taps, int boundary, int n_tapers);
+
 /* Backward of pb_compute_polynomial_taps with not_symmetric != 0 (deblurring.compute_polynomial_fft with the pure-phase filter,
  * deblurring.py:141-169; p2o: filters.py:255-273).  H x W is the whole circular domain.  With K = fft2(p2o(kernel)), r = |K|,
  * C = conj(K) / (r + 1e-8), P the polynomial of K, P' its derivative, M = C P, N = H W, g = grad_out:

@@ -6,7 +6,8 @@ The compute path is hand-written HIP for gfx950 behind the C ABI in
 first call.  There is no CPU fallback: without the library or a GPU the calls raise.
 """
 from .deblurring import polyblur_deblurring, polyblur_deblurring_uint8, PolyblurDeblurring  # noqa: F401
-# the non-blind step with a kernel of the caller's (reference deblurring.py:211-239, filters.py:14-37, edgetaper.py:26-33)
+# the non-blind step with a kernel of the caller's (reference deblurring.py:211-239, filters.py:14-37, edgetaper.py:26-33);
+# all three differentiable with respect to the image and the kernel, the edgetaper through its weights too
 from .nonblind import inverse_filtering_rank3, convolve2d, edgetaper  # noqa: F401
 # ... and for kernels that are not point-symmetric: the pure-phase filter (reference deblurring.py:113-169, not_symmetric=True),
 # differentiable with respect to the image and the kernel like the three above

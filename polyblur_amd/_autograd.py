@@ -78,6 +78,42 @@ class TapsFunction(torch.autograd.Function):
         return gx, gk, None, None, None, None, None, None
 
 
+class EdgetaperFunction(torch.autograd.Function):
+    """edgetaper of a ROCm float32 image that is the whole domain: ``n_tapers`` blends, differentiated with respect to
+    the image and to the kernel -- through the taper weights too; odd kernel sides.  The arguments are TapsFunction's, with the
+    blend count in poly's place; the forward is the one call of pb_edgetaper_taps, so its bits are those under torch.no_grad()."""
+
+    @staticmethod
+    def forward(ctx, img, kernel, taps, eshape, bnd, n_tapers, correlate, call):
+        x = img.detach()
+        (out,), _ = staged(x, np.float32, call, taps=taps)
+        ctx.save_for_backward(x)
+        ctx.pb = (taps, bnd, int(n_tapers), bool(correlate), int(img.shape[0]), eshape)
+        ctx.kernel_like = None if kernel is None else (tuple(int(v) for v in kernel.shape), kernel.dtype, kernel.device)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        (x,) = ctx.saved_tensors
+        taps, bnd, n_tapers, correlate, B, eshape = ctx.pb
+        want_x, want_k = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        xin = x.contiguous()
+        g = _upstream(grad_out)
+        gx = torch.empty_like(xin) if want_x else None
+        gk = torch.empty(taps.shape, dtype=torch.float32, device=x.device) if want_k else None
+        with bound_engine(x) as eng:
+            ks = eng.set_taps(taps)
+            try:
+                eng.edgetaper_taps_backward_ptr(xin.data_ptr(), g.data_ptr(), gx.data_ptr() if want_x else None,
+                                                gk.data_ptr() if want_k else None, eshape, ks, bnd, n_tapers)
+            finally:
+                ks.free()                               # (waits for the stream)
+        if want_k:
+            gk = _kernel_grad(gk, ctx.kernel_like, B, correlate)
+        return gx, gk, None, None, None, None, None, None
+
+
 class PhaseFunction(torch.autograd.Function):
     """compute_polynomial(method='fft', not_symmetric=True) of a ROCm float32 image that is the whole domain; kernel
     sides even or odd.  The arguments are TapsFunction's, with poly = (alpha, b)."""

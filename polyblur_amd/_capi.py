@@ -41,6 +41,7 @@ SYMBOLS = [
     "pb_taps_create", "pb_taps_free", "pb_convolve2d_taps", "pb_edgetaper_taps", "pb_inverse_filter_taps",
     "pb_compute_polynomial_taps", "pb_inverse_filter_phase_taps", "pb_set_phase_budget",
     "pb_tap_gradient", "pb_convolve2d_taps_backward", "pb_compute_polynomial_taps_backward", "pb_compute_polynomial_phase_taps_backward",
+    "pb_edgetaper_taps_backward",
     "pb_estimate_blur_backward",
     "pb_fourier_gradients_backward", "pb_halo_mask_backward", "pb_bilateral_backward",
     "pb_dt_recursive_filter_backward",
@@ -150,6 +151,7 @@ def load_library():
             "pb_tap_gradient": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, ci, vp]),
             "pb_convolve2d_taps_backward": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, ci]),
             "pb_compute_polynomial_taps_backward": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, cf, cf, ci]),
+            "pb_edgetaper_taps_backward": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, ci, ci]),
             "pb_compute_polynomial_phase_taps_backward": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, cf, cf]),
             "pb_estimate_blur_backward": (ci, [vp, vp, ci, ci, ci, ci, C.POINTER(pb_options), vp, vp, vp, ci, vp]),
             "pb_halo_mask": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci]),

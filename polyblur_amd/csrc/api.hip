@@ -1532,6 +1532,85 @@ int pb_compute_polynomial_taps_backward(pb_ctx *ctx, const float *x, const float
     return PB_OK;
 }
 
+int pb_edgetaper_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps, int B, int C, int H,
+                               int W, const pb_taps *taps, int boundary, int n_tapers) {
+    int rc = check_shape(ctx, PB_F32, B, C, H, W);
+    if (rc) return rc;
+    rc = backward_args(ctx, "pb_edgetaper_taps_backward", x, grad_out, grad_x, grad_taps, taps);
+    if (rc) return rc;
+    if (n_tapers < 0) return pb_fail(ctx, PB_ERR_BADARG, "n_tapers < 0");
+    if (B > 65535) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "pb_edgetaper_taps_backward: %d images (the kernels' grids take up to 65535)", B);
+    Geometry g; const pb_blur_info *recs = nullptr;
+    rc = taps_geometry(ctx, taps, B, C, H, W, boundary, true, true, &g, &recs);
+    if (rc) return rc;
+    PB_HIP(hipSetDevice(ctx->device));
+    g.pp = W; g.pplane = g.HW;
+    const size_t bytes = sizeof(float) * g.P * g.HW;
+    const size_t tap_bytes = sizeof(float) * (size_t)B * taps->kh * taps->kw;
+    if (n_tapers == 0) {
+        if (grad_x) PB_HIP(hipMemcpyAsync(grad_x, grad_out, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (grad_taps) PB_HIP(hipMemsetAsync(grad_taps, 0, tap_bytes, ctx->stream));
+        return PB_OK;
+    }
+    // the autocorrelations the forward's blends read: the boundary's records, or the set's table
+    TaperAcorr ac;
+    if (taps->tables) { ac.acy = g.big.acorr; ac.acx = g.big.acorr + PB_BIG_ACORR / 2; ac.stride = PB_BIG_ACORR; ac.nlag = PB_KSIZE_MAX; }
+    else { ac.acy = recs->acorr_y; ac.acx = recs->acorr_x; ac.stride = (long)(sizeof(pb_blur_info) / sizeof(float)); ac.nlag = PB_KSIZE; }
+    Geometry ga = g; const pb_blur_info *arecs = nullptr;
+    taps_adjoint(taps, boundary, &ga, &arecs);
+    float *u = static_cast<float *>(pb_scratch(ctx, "etg.u", bytes)), *ag = static_cast<float *>(pb_scratch(ctx, "etg.ag", bytes));
+    float *gb = n_tapers > 1 ? static_cast<float *>(pb_scratch(ctx, "etg.g", bytes)) : nullptr;
+    if (!u || !ag || (n_tapers > 1 && !gb)) return PB_ERR_NOMEM;
+    float *xs = nullptr, *kx = nullptr, *abar = nullptr;
+    if (grad_taps) {
+        // x_1 .. x_{n-1}: the forward's blends again, pass for pass (the forward keeps nothing), each into a plane set of its own
+        kx = static_cast<float *>(pb_scratch(ctx, "etg.kx", bytes));
+        abar = static_cast<float *>(pb_scratch(ctx, "etg.abar", sizeof(float) * (size_t)B * g.HW));
+        if (!kx || !abar) return PB_ERR_NOMEM;
+        if (n_tapers > 1) {
+            xs = static_cast<float *>(pb_scratch(ctx, "etg.x", bytes * (size_t)(n_tapers - 1)));
+            if (!xs) return PB_ERR_NOMEM;
+        }
+        ConvPass p = base_pass(g, recs, boundary);
+        p.epilogue = EPI_TAPER;
+        const float *src = x;
+        for (int i = 0; i + 1 < n_tapers; ++i) {
+            float *dst = xs + (size_t)i * g.P * g.HW;
+            set_in_padded(p, g, src); set_x_padded(p, g, src); set_out_padded(p, g, dst);
+            rc = taps_pass(ctx, g, p);
+            if (rc) return rc;
+            src = dst;
+        }
+    }
+    const float *gn = grad_out;
+    for (int i = n_tapers - 1; i >= 0; --i) {
+        const float *xi = !grad_taps ? nullptr : i == 0 ? x : xs + (size_t)(i - 1) * g.P * g.HW;
+        if (grad_taps) {
+            ConvPass p = base_pass(g, recs, boundary);          // K x_i, for Abar
+            set_in_padded(p, g, xi); set_x_padded(p, g, xi); set_out_padded(p, g, kx);
+            rc = taps_pass(ctx, g, p);
+            if (rc) return rc;
+        }
+        rc = pb_launch_taper_blend_adjoint(ctx, ac, xi, kx, gn, u, ag, abar, i == n_tapers - 1, B, C, H, W);
+        if (rc) return rc;
+        if (grad_taps) {
+            rc = pb_launch_tap_gradient(ctx, u, xi, B, C, H, W, taps->kh, taps->kw, boundary, 1.f, i != n_tapers - 1, grad_taps);
+            if (rc) return rc;
+        }
+        if (i == 0 && !grad_x) break;                           // (g_0 is the image gradient: nobody asked)
+        // g_i = K^T u + A g: the pass with the set's other orientation, ag as its x operand
+        float *dst = i == 0 ? grad_x : gb;
+        ConvPass p = base_pass(ga, arecs, boundary);
+        p.scale = 1.f; p.coef = 1.f;
+        set_in_padded(p, ga, u); set_x_padded(p, ga, ag); set_out_padded(p, ga, dst);
+        rc = taps_pass(ctx, ga, p);
+        if (rc) return rc;
+        gn = dst;
+    }
+    if (grad_taps) return pb_launch_taper_weight_chain(ctx, ac, abar, taps->raw, taps->kh, taps->kw, B, H, W, grad_taps);
+    return PB_OK;
+}
+
 int pb_compute_polynomial_phase_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps, int B,
                                               int C, int H, int W, const pb_taps *taps, float alpha, float beta) {
     static const char *who = "pb_compute_polynomial_phase_taps_backward";

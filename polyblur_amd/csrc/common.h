@@ -361,6 +361,18 @@ int pb_launch_tap_gradient(pb_ctx *ctx, const float *u, const float *v, int B, i
                            float scale, int accumulate, float *grad);
 int pb_tap_gradient_groups(int B, int C, int H, int W);
 
+// the backward of an edgetaper blend (edgetaper_grad.hip).  TaperAcorr: where the forward reads the kernel's
+// two autocorrelations -- image b's at acy + b * stride and acx + b * stride, nlag lags stored (25 in a record, 49 in a table).
+struct TaperAcorr { const float *acy, *acx; long stride; int nlag; };
+// one blend: u = (1 - A) g, ag = A g, and -- abar not null -- abar[b] (= when first, += otherwise) the sum over the image's C
+// planes of g (x - kx), kx = K x.  (B,C,H,W) fp32 planes that are the whole domain; abar: B planes of H x W
+int pb_launch_taper_blend_adjoint(pb_ctx *ctx, const TaperAcorr &ac, const float *x, const float *kx, const float *g, float *u, float *ag,
+                                  float *abar, int first, int B, int C, int H, int W);
+// abar -> vbar ("etg.vbar", B * (H + W) floats: the ring's rows, then its columns) -> kbar_y, kbar_x; grad_taps[b][i][j] +=
+// kbar_y[i] + kbar_x[j].  raw: the B kh x kw kernels as the caller gave them (device)
+int pb_launch_taper_weight_chain(pb_ctx *ctx, const TaperAcorr &ac, const float *abar, const float *raw, int kh, int kw, int B, int H, int W,
+                                 float *grad_taps);
+
 // ------------------------------------------------------------------------------------
 // estimation (estimate.hip)
 // ------------------------------------------------------------------------------------

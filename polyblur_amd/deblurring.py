@@ -25,8 +25,8 @@ live code path is the bilateral one, deblurring.py:107-108), ``return_info``, ``
 ('fp32' | 'fp16': float16 tensors only -- store the two Horner temporaries as fp16).
 
 A float32 ROCm tensor that requires grad takes the differentiable composition (``_blind_under_grad``): estimation, non-blind
-step, ``remove_halo=True`` and ``prefiltering=True`` with the bilateral prefilter have the engine's own backward passes;
-``edgetaping``, the other two prefilters, ``q > 0`` and the patch decomposition are refused before any device work.
+step, ``remove_halo=True``, ``edgetaping=True`` and ``prefiltering=True`` with the bilateral prefilter have the engine's own
+backward passes; the other two prefilters, ``q > 0`` and the patch decomposition are refused before any device work.
 """
 from __future__ import annotations
 
@@ -144,7 +144,7 @@ def _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_i
     what = "polyblur_deblurring"
     if remove_halo and not (img.is_cuda and img.dtype == torch.float32):     # (the stage's device check first: its reason names the stage)
         refuse_under_grad(what + "(remove_halo=True)", HALO_ONLY)
-    if edgetaping:
+    if edgetaping and not (img.is_cuda and img.dtype == torch.float32):      # (the edgetaper's backward is the engine's: 4.15)
         refuse_under_grad(what + "(edgetaping=True)", NO_EDGETAPER)
     if prefiltering:
         rocm_float32 = img.is_cuda and img.dtype == torch.float32
@@ -180,10 +180,11 @@ def _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_i
                                           ker_size=ker_size, discard_saturation=discard_saturation, multichannel=multichannel_kernel)
         if prefiltering:                                                     # (deblurring.py:80-84; the mask's x is the smooth part)
             smooth, noise = edge_aware_filtering(x, sigma_s, sigma_r, prefilter=prefilter)
-            x = (inverse_filtering_rank3(smooth, kernel, alpha, beta, remove_halo=bool(remove_halo), grad_img=grad_img, method=method)
-                 + noise).clip(0, 1)
+            x = (inverse_filtering_rank3(smooth, kernel, alpha, beta, remove_halo=bool(remove_halo), do_edgetaper=bool(edgetaping),
+                                         grad_img=grad_img, method=method) + noise).clip(0, 1)
         else:
-            x = inverse_filtering_rank3(x, kernel, alpha, beta, remove_halo=bool(remove_halo), grad_img=grad_img, method=method).clip(0, 1)
+            x = inverse_filtering_rank3(x, kernel, alpha, beta, remove_halo=bool(remove_halo), do_edgetaper=bool(edgetaping),
+                                        grad_img=grad_img, method=method).clip(0, 1)
     return x if n_iter > 0 else img.clone()
 
 

@@ -338,6 +338,13 @@ class Engine:
         self._check(self.lib.pb_compute_polynomial_phase_taps_backward(self.ctx, x_ptr, grad_out_ptr, grad_x_ptr, grad_taps_ptr, B, Cc, H,
                                                                        W, ks.handle, float(alpha), float(beta)))
 
+    def edgetaper_taps_backward_ptr(self, x_ptr, grad_out_ptr: int, grad_x_ptr, grad_taps_ptr, shape, ks: KernelSet,
+                                    boundary=capi.PB_WRAP, n_tapers=3):
+        """the same for edgetaper, through the taper weights as well (pb_edgetaper_taps_backward)"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_edgetaper_taps_backward(self.ctx, x_ptr, grad_out_ptr, grad_x_ptr, grad_taps_ptr, B, Cc, H, W,
+                                                        ks.handle, int(boundary), int(n_tapers)))
+
     # ---- the blind estimation on device pointers, and its backward pass --------------------------------------------------
     def estimate_blur_ptr(self, in_ptr: int, dtype: int, shape, opts: capi.pb_options, info_ptr: int):
         """B records into device memory at info_ptr (pb_estimate_blur); asynchronous on the context's stream"""

@@ -31,16 +31,19 @@ that requires grad -- with respect to the image and to the taps (not to alpha an
 are the engine's too (pb_convolve2d_taps_backward, pb_compute_polynomial_taps_backward); the pad, crop and clamp of
 ``inverse_filtering_rank3`` are then torch's own ops -- the replicate pad composed of slices, expand and cat, whose backward is
 an ordered sum where F.pad's adds with float atomics.  ``remove_halo=True`` under grad is ``halo_masking`` (halo.py; DESIGN.md
-4.9) between the crop and the clamp, differentiable with respect to ``grad_img`` too.  Under grad: float32 ROCm tensors and odd
-kernel sides only, and no ``do_edgetaper`` or ``edgetaper()`` (NotImplementedError before any device work).  Without grad
-nothing changes: the calls below run as before.
+4.9) between the crop and the clamp, differentiable with respect to ``grad_img`` too.  ``edgetaper()`` and ``do_edgetaper=True`` are
+differentiable as well: the backward of the blends is the engine's pb_edgetaper_taps_backward, with respect to the
+image and to the kernel -- through the taper weights too, which are autocorrelations of the kernel's projections; under grad
+``inverse_filtering_rank3(do_edgetaper=True)`` is replicate pad -> three blends -> polynomial -> crop -> [halo masking of the
+tapered, cropped image] -> clamp.  Under grad: float32 ROCm tensors and odd kernel sides only (NotImplementedError before any
+device work).  Without grad nothing changes: the calls below run as before.
 
 ``compute_polynomial(..., not_symmetric=True)`` and ``inverse_filtering_nonsymmetric`` are differentiable in the same way (DESIGN.md
 4.14): the backward of the pure-phase polynomial is the engine's pb_compute_polynomial_phase_taps_backward -- the image gradient
 is the forward's transform with the conjugate multiplier, the tap gradient a gather from one more transform, through the phase
 factor conj(K) / |K| as well --, and ``inverse_filtering_nonsymmetric`` is composed as ``inverse_filtering_rank3`` is.  Kernel
-sides even or odd: nothing in that adjoint is centred.  Under grad: float32 ROCm tensors, no ``do_edgetaper``, padded sides the
-engine holds in LDS.  With no ROCm tensor among the operands the refusal is the one it has always been ("the pure-phase filter is
+sides even or odd: nothing in that adjoint is centred.  Under grad: float32 ROCm tensors, no ``do_edgetaper`` (the edgetaper's
+backward takes odd sides and is not wired in front of the pure-phase filter), padded sides the engine holds in LDS.  With no ROCm tensor among the operands the refusal is the one it has always been ("the pure-phase filter is
 not differentiated").
 
 The arithmetic is the HIP engine's (include/polyblur_hip.h: pb_taps_create and the *_taps calls); nothing runs on the CPU.
@@ -135,6 +138,19 @@ def _apply_phase_function(img, kernel, taps, eshape, alpha, b, correlate=False):
     return PhaseFunction.apply(img, kernel if is_tensor(kernel) else None, taps, eshape, (alpha, b), correlate, call)
 
 
+def _taper_operands(img, kernel):
+    """what the edgetaper's backward is built for: a float32 ROCm image, and no CPU kernel that requires grad (anything else under
+    grad keeps the refusal it has always had)"""
+    return is_rocm_float32(img) and not (is_tensor(kernel) and kernel.requires_grad and not kernel.is_cuda)
+
+
+def _apply_edgetaper_function(img, kernel, taps, eshape, bnd, n_tapers, correlate=False):
+    """edgetaper of ``img``, the whole domain, inside the graph"""
+    from ._autograd import EdgetaperFunction
+    call = lambda eng, i, o, ex, ks: eng.edgetaper_taps_ptr(i, o[0], eshape, ks, bnd, n_tapers)
+    return EdgetaperFunction.apply(img, kernel if is_tensor(kernel) else None, taps, eshape, bnd, n_tapers, correlate, call)
+
+
 def convolve2d(img, kernel, method='direct'):
     """filters.convolve2d (filters.py:14-37) with a 2-D kernel: ``img`` is the whole domain."""
     shape, dt = check_image(img, allow_half=False)
@@ -149,14 +165,18 @@ def convolve2d(img, kernel, method='direct'):
 
 def edgetaper(img, kernel, n_tapers=3, method='fft'):
     """edgetaper.edgetaper (edgetaper.py:26-33): ``n_tapers`` blends of ``img`` with its blurred self, weighted by the
-    autocorrelations of the kernel's projections."""
+    autocorrelations of the kernel's projections.  Differentiable with respect to ``img`` and ``kernel`` (float32 ROCm tensors,
+    odd kernel sides)."""
     shape, dt = check_image(img, allow_half=False)
     if not isinstance(n_tapers, (int, np.integer)) or n_tapers < 0:
         raise ValueError("n_tapers must be an integer >= 0")
     taps, eshape = _check_kernel(kernel, method, shape, pad_domain=False, circular_only=True)
-    if wants_grad(img, kernel):
-        refuse_under_grad("edgetaper", "the blends are not differentiated (call it under torch.no_grad() or on detached tensors)")
     bnd = _BOUNDARY[method]
+    if wants_grad(img, kernel):
+        if not _taper_operands(img, kernel):
+            refuse_under_grad("edgetaper", "the blends are not differentiated (call it under torch.no_grad() or on detached tensors)")
+        _check_grad(img, kernel, "edgetaper")
+        return _apply_edgetaper_function(img, kernel, taps, eshape, bnd, int(n_tapers))
     return _run(img, dt, taps, lambda eng, i, o, ex, ks: eng.edgetaper_taps_ptr(i, o[0], eshape, ks, bnd, int(n_tapers)))
 
 
@@ -189,7 +209,7 @@ def inverse_filtering_rank3(img, kernel, alpha=2, b=4, correlate=False, remove_h
         # (the stage's device check first: its reason names the stage; the kernel's own checks follow: _check_grad)
         if remove_halo and not all(is_rocm_float32(t) for t in (img,) + halo_planes):
             refuse_under_grad("inverse_filtering_rank3(remove_halo=True)", HALO_ONLY)
-        if do_edgetaper:
+        if do_edgetaper and not _taper_operands(img, kernel):
             refuse_under_grad("inverse_filtering_rank3(do_edgetaper=True)", NO_EDGETAPER)
         _check_grad(img, kernel, "inverse_filtering_rank3")
         # pad, crop and clamp are torch's own ops with torch's own backward; the polynomial and the mask are the engine's
@@ -201,6 +221,10 @@ def inverse_filtering_rank3(img, kernel, alpha=2, b=4, correlate=False, remove_h
         pad = taps.shape[-1] // 2
         xp = replicate_pad(img, pad)                          # (the polynomial's domain: the engine's shape with the padded sides)
         pshape = eshape[:2] + tuple(xp.shape[-2:])
+        if do_edgetaper:                                      # (three blends of the padded plane: deblurring.py:229-230)
+            xp = _apply_edgetaper_function(xp, kernel, taps, pshape, bnd, 3, bool(correlate))
+            if remove_halo:
+                img = xp[..., pad:-pad, pad:-pad]             # (the mask's image is the tapered one: deblurring.py:236-238)
         y = _apply_taps_function(xp, kernel, taps, pshape, bnd, (alpha, b),
                                  lambda eng, i, o, ex, ks: eng.compute_polynomial_taps_ptr(i, o[0], pshape, ks, alpha, b, bnd, False), bool(correlate))
         y = y[..., pad:-pad, pad:-pad]
