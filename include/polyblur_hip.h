@@ -367,6 +367,21 @@ int pb_convolve2d_taps_backward(pb_ctx *ctx, const float *x, const float *grad_o
 int pb_compute_polynomial_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps,
                                         int B, int C, int H, int W, const pb_taps *taps, float alpha, float beta, int boundary);
 
+/* The polynomial's own parameters: d loss / d alpha = 1/2 <G, K (1 - K)^2 x> and d loss / d beta = <G, (1 - K)^3 x>
+ * for out = pb_compute_polynomial_taps(x) with not_symmetric == 0 and G = grad_out.  Evaluated in that factored form -- the detail
+ * images u1 = x - K x, u2 = u1 - K u1, u3 = u2 - K u2 by three explicit Horner steps of the forward's pass under the call's boundary,
+ * then one reduction  d beta = sum G u3,  d alpha = 1/2 sum G (u2 - u3)  -- because the sums of <G, K^i x> they expand to cancel a
+ * hundredfold in fp32 on a blurred image.  grad_params: DEVICE memory, (B,2): (d / d alpha, d / d beta) per image as the engine
+ * counts images (B; with one kernel per plane the caller passes B*C one-channel images); written, not accumulated.  alpha and beta
+ * are taken for symmetry with the forward: the polynomial is linear in both, neither gradient depends on them.  The argument rules
+ * and refusals of pb_compute_polynomial_taps_backward: ODD kh and kw (PB_ERR_UNSUPPORTED), the fit and shape checks; x, grad_out or
+ * grad_params NULL, or grad_params aliasing an input: PB_ERR_BADARG; B above 65535: PB_ERR_UNSUPPORTED; every refusal before any
+ * launch.  Scratch: two plane sets of the domain, "ppg.u1" (u1, then u3) and "ppg.u2", and the partials "ppg.partial".  Sums in
+ * double at every level in an order the shape alone fixes, no float atomics: the same call gives the same bits, and operands at
+ * any element offset give the aligned call's bits.  pb_compute_polynomial_taps_backward is untouched by it.                  */
+int pb_compute_polynomial_taps_params_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_params,
+                                               int B, int C, int H, int W, const pb_taps *taps, float alpha, float beta, int boundary);
+
 /* Backward of pb_edgetaper_taps (edgetaper.edgetaper, edgetaper.py:10-33), with respect to the image and to the taps -- the taper
  * weights A = v1 (x) v2 are functions of the kernel (autocorrelations of its projections, normalised per kernel: the "per-image
  * maximum" above) and are differentiated too.  With x_0 = x, x_{i+1} = A x_i + (1 - A) (K x_i) and g_n = grad_out, for
@@ -421,6 +436,16 @@ int pb_compute_polynomial_phase_taps_backward(pb_ctx *ctx, const float *x, const
 int pb_estimate_blur_backward(pb_ctx *ctx, const float *in, int B, int C, int H, int W, const pb_options *opt,
                               const pb_blur_info *dev_info, const float *grad_kernel, const float *grad_sigma_rho,
                               int ker_size, float *grad_in);
+
+/* pb_estimate_blur_backward with one more output: grad_cb (device, (B,2); written) = d loss / d (c, b) of the
+ * affine model sigma^2 = c^2 / (m^2 + 1e-8) - b^2 per image, from the same scalar chain: with dv_e = d loss / d (sigma^2, rho^2),
+ * d c = sum_e dv_e 2 c / (m_e^2 + 1e-8), d b = -2 b sum_e dv_e, in double, rounded once.  A clamped sigma^2 or rho^2 contributes
+ * exactly 0 (the clamp's state is the forward's record's).  grad_in or grad_cb may be NULL, not both; with grad_in NULL the scatter
+ * is not launched; with both, grad_in has the bits it has alone.  pb_estimate_blur_backward is this call with grad_cb == NULL:
+ * the same launches, the same bits.  Every other rule, refusal and scratch name as above.                                      */
+int pb_estimate_blur_params_backward(pb_ctx *ctx, const float *in, int B, int C, int H, int W, const pb_options *opt,
+                                     const pb_blur_info *dev_info, const float *grad_kernel, const float *grad_sigma_rho,
+                                     int ker_size, float *grad_in, float *grad_cb);
 
 /* The pure-phase polynomial takes the plane pairs of an image in groups whose complex scratch (one Hp x Wp float2 plane per
  * pair) stays within `bytes`; one pair is always allowed.  0 = the default, 256 MiB.  Results do not depend on it.       */

@@ -78,6 +78,57 @@ class TapsFunction(torch.autograd.Function):
         return gx, gk, None, None, None, None, None, None
 
 
+def _param_grad(rows, p):
+    """the engine's per-image rows of a parameter's gradient -- a (B',) float32 device tensor -- summed in index order in float64,
+    in the shape, dtype and device of the parameter tensor ``p``"""
+    return rows.to(torch.float64).cumsum(0)[-1].to(device=p.device, dtype=p.dtype).reshape(p.shape)
+
+
+class TapsParamsFunction(torch.autograd.Function):
+    """compute_polynomial with alpha and / or b as one-element tensors that require grad: TapsFunction with the two
+    parameter tensors (either may be None) behind the kernel.  The forward is TapsFunction's, with poly = the parameters' float values;
+    the backward runs pb_compute_polynomial_taps_backward only where the image or the kernel asks, and
+    pb_compute_polynomial_taps_params_backward only where a parameter does."""
+
+    @staticmethod
+    def forward(ctx, img, kernel, alpha_t, beta_t, taps, eshape, bnd, poly, correlate, call):
+        x = img.detach()
+        (out,), _ = staged(x, np.float32, call, taps=taps)
+        ctx.save_for_backward(x, *(t for t in (alpha_t, beta_t) if t is not None))
+        ctx.pb = (taps, bnd, poly, bool(correlate), int(img.shape[0]), eshape, alpha_t is not None, beta_t is not None)
+        ctx.kernel_like = None if kernel is None else (tuple(int(v) for v in kernel.shape), kernel.dtype, kernel.device)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, params = ctx.saved_tensors[0], list(ctx.saved_tensors[1:])
+        taps, bnd, poly, correlate, B, eshape, has_a, has_b = ctx.pb
+        alpha_t = params.pop(0) if has_a else None
+        beta_t = params.pop(0) if has_b else None
+        want_x, want_k, want_a, want_b = ctx.needs_input_grad[:4]
+        xin = x.contiguous()
+        g = _upstream(grad_out)
+        gx = torch.empty_like(xin) if want_x else None
+        gk = torch.empty(taps.shape, dtype=torch.float32, device=x.device) if want_k else None
+        gp = torch.empty((int(eshape[0]), 2), dtype=torch.float32, device=x.device) if want_a or want_b else None
+        with bound_engine(x) as eng:
+            ks = eng.set_taps(taps)
+            try:
+                if want_x or want_k:
+                    eng.compute_polynomial_taps_backward_ptr(xin.data_ptr(), g.data_ptr(), gx.data_ptr() if want_x else None,
+                                                             gk.data_ptr() if want_k else None, eshape, ks, poly[0], poly[1], bnd)
+                if gp is not None:
+                    eng.compute_polynomial_taps_params_backward_ptr(xin.data_ptr(), g.data_ptr(), gp.data_ptr(), eshape, ks, poly[0], poly[1], bnd)
+            finally:
+                ks.free()                               # (waits for the stream)
+        if want_k:
+            gk = _kernel_grad(gk, ctx.kernel_like, B, correlate)
+        ga = _param_grad(gp[:, 0], alpha_t) if want_a else None
+        gb = _param_grad(gp[:, 1], beta_t) if want_b else None
+        return gx, gk, ga, gb, None, None, None, None, None, None
+
+
 class EdgetaperFunction(torch.autograd.Function):
     """edgetaper of a ROCm float32 image that is the whole domain: ``n_tapers`` blends, differentiated with respect to
     the image and to the kernel -- through the taper weights too; odd kernel sides.  The arguments are TapsFunction's, with the
@@ -179,6 +230,48 @@ class EstimationFunction(torch.autograd.Function):
             eng.estimate_blur_backward_ptr(x.data_ptr(), x.shape, opts, rec.data_ptr(), gk.data_ptr() if filters else None,
                                            None if filters else gsr.data_ptr(), ker_size if filters else capi.PB_KSIZE, gin.data_ptr())
         return gin, None, None, None, None, None
+
+
+class EstimationParamsFunction(torch.autograd.Function):
+    """gaussian_blur_estimation with c and / or b of the affine model as one-element tensors that require grad:
+    EstimationFunction with the two parameter tensors (either may be None) behind the image.  The backward is one call of
+    pb_estimate_blur_params_backward: the image's gradient only where the image asks (no scatter otherwise), the (B,2) rows of
+    d loss / d (c, b) only where a parameter does."""
+
+    @staticmethod
+    def forward(ctx, img, c_t, b_t, opts, ker_size, filters, records, unpack):
+        x = img.detach().contiguous()
+        rec = records(x)
+        ctx.save_for_backward(x, rec, *(t for t in (c_t, b_t) if t is not None))
+        ctx.pb = (opts, int(ker_size), bool(filters), c_t is not None, b_t is not None)
+        out = unpack(rec)
+        if not filters:
+            ctx.mark_non_differentiable(out[2])               # (theta comes from integer tensors: blur_estimation.py:160-167)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        x, rec = ctx.saved_tensors[:2]
+        params = list(ctx.saved_tensors[2:])
+        opts, ker_size, filters, has_c, has_b = ctx.pb
+        c_t = params.pop(0) if has_c else None
+        b_t = params.pop(0) if has_b else None
+        want_x, want_c, want_b = ctx.needs_input_grad[:3]
+        gk = gsr = None
+        if filters:
+            gk = _upstream(grads[0])
+        else:
+            gsr = torch.cat([grads[0].detach().to(torch.float32).reshape(-1, 1), grads[1].detach().to(torch.float32).reshape(-1, 1)], dim=1).contiguous()
+        gin = torch.empty_like(x) if want_x else None
+        gcb = torch.empty((int(x.shape[0]), 2), dtype=torch.float32, device=x.device) if want_c or want_b else None
+        with bound_engine(x) as eng:
+            eng.estimate_blur_params_backward_ptr(x.data_ptr(), x.shape, opts, rec.data_ptr(), gk.data_ptr() if filters else None,
+                                                  None if filters else gsr.data_ptr(), ker_size if filters else capi.PB_KSIZE,
+                                                  None if gin is None else gin.data_ptr(), None if gcb is None else gcb.data_ptr())
+        gc = _param_grad(gcb[:, 0], c_t) if want_c else None
+        gb = _param_grad(gcb[:, 1], b_t) if want_b else None
+        return gin, gc, gb, None, None, None, None, None
 
 
 class FourierGradientsFunction(torch.autograd.Function):

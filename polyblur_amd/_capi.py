@@ -41,8 +41,8 @@ SYMBOLS = [
     "pb_taps_create", "pb_taps_free", "pb_convolve2d_taps", "pb_edgetaper_taps", "pb_inverse_filter_taps",
     "pb_compute_polynomial_taps", "pb_inverse_filter_phase_taps", "pb_set_phase_budget",
     "pb_tap_gradient", "pb_convolve2d_taps_backward", "pb_compute_polynomial_taps_backward", "pb_compute_polynomial_phase_taps_backward",
-    "pb_edgetaper_taps_backward",
-    "pb_estimate_blur_backward",
+    "pb_edgetaper_taps_backward", "pb_compute_polynomial_taps_params_backward",
+    "pb_estimate_blur_backward", "pb_estimate_blur_params_backward",
     "pb_fourier_gradients_backward", "pb_halo_mask_backward", "pb_bilateral_backward",
     "pb_dt_recursive_filter_backward",
     "pb_comm_shard", "pb_comm_unique_id", "pb_comm_init", "pb_comm_destroy", "pb_comm_scatter", "pb_comm_gather",
@@ -154,6 +154,8 @@ def load_library():
             "pb_edgetaper_taps_backward": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, ci, ci]),
             "pb_compute_polynomial_phase_taps_backward": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, cf, cf]),
             "pb_estimate_blur_backward": (ci, [vp, vp, ci, ci, ci, ci, C.POINTER(pb_options), vp, vp, vp, ci, vp]),
+            "pb_estimate_blur_params_backward": (ci, [vp, vp, ci, ci, ci, ci, C.POINTER(pb_options), vp, vp, vp, ci, vp, vp]),
+            "pb_compute_polynomial_taps_params_backward": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp, cf, cf, ci]),
             "pb_halo_mask": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci]),
             "pb_fourier_gradients_backward": (ci, [vp, vp, vp, ci, ci, ci, vp]),
             "pb_halo_mask_backward": (ci, [vp] * 10 + [ci, ci, ci, ci]),

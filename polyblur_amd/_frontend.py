@@ -30,6 +30,8 @@ FLOAT32_ONLY = "gradients are built for float32 images"
 NO_QUANTILE = "the backward of torch.quantile is not built -- pass q=0, which is what the blind driver defaults to"
 NO_EDGETAPER = "the edgetaper is not differentiated"
 CPU_WITH_GRAD = "%s requires grad and is a CPU tensor -- gradients are built for ROCm tensors only"
+PARAM_NOT_ROCM = "%s requires grad and the image is not a float32 ROCm tensor -- parameter gradients are built for float32 ROCm images only"
+NO_PHASE_PARAMS = "the gradients with respect to alpha and b are not built for the pure-phase filter"
 
 
 # ---- predicates and checks ------------------------------------------------------------------------------------------------
@@ -118,6 +120,37 @@ def wants_grad(*operands) -> bool:
 
 def refuse_under_grad(what, reason):
     raise NotImplementedError("%s has no backward pass: %s" % (what, reason))
+
+
+# ---- learnable parameters ------------------------------------------------------------------------------------
+def check_param(p, name, img=None):
+    """A scalar parameter (alpha, beta, c, b) is a Python number or a one-element tensor -- 0-dim or (1,), float32 or float64, on the
+    CPU or on the device of the image ``img`` (ValueError otherwise).  -> the tensor where autograd is on and it requires grad, else
+    None.  Reads nothing from a device: the value is read later, once, by ``param_value``."""
+    if not is_tensor(p):
+        return None
+    import torch
+    if p.numel() != 1 or p.dim() > 1:
+        raise ValueError("%s must be a number or a one-element tensor (0-dim or of shape (1,)), got shape %r" % (name, tuple(p.shape)))
+    if p.dtype not in (torch.float32, torch.float64):
+        raise TypeError("%s: a tensor parameter must be float32 or float64" % name)
+    if p.device.type != "cpu" and not (is_tensor(img) and img.device == p.device):
+        raise ValueError("%s lives on %s and the image on %s: a tensor parameter lives on the CPU or on the image's device"
+                         % (name, p.device, img.device if is_tensor(img) else "the host"))
+    return p if p.requires_grad and torch.is_grad_enabled() else None
+
+
+def param_value(p):
+    """the number the engine runs with: ``float(t)`` of a tensor parameter -- one synchronisation when it lives on a device (the
+    launch plan sizes window halos from the coefficients on the host) --, a Python number as it is"""
+    return float(p.detach()) if is_tensor(p) else p
+
+
+def refuse_params(what, img, **params):
+    """a parameter that requires grad beside an image that is not a float32 ROCm tensor; params: name -> check_param's result"""
+    for name, t in params.items():
+        if t is not None and not is_rocm_float32(img):
+            refuse_under_grad(what, PARAM_NOT_ROCM % name)
 
 
 def build_options(C, n_iter, c, b, alpha, beta, sigma_r, sigma_s, ker_size, q, n_angles, n_interpolated_angles,

@@ -1234,6 +1234,15 @@ void taps_adjoint(const pb_taps *t, int boundary, Geometry *g, const pb_blur_inf
     else *recs = boundary == PB_WRAP ? t->rec_zero : t->rec_wrap;
 }
 
+// The adjoint of an even kernel side sits one sample off the forms a set holds: every backward call that runs a pass with the set's
+// other orientation, or the forward's own pass on the way to a gradient, takes odd sides only.  taps may be null (no rule)
+int odd_sides_only(pb_ctx *ctx, const char *who, const pb_taps *taps) {
+    if (taps && (!(taps->kh & 1) || !(taps->kw & 1)))
+        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "%s: a %d x %d kernel -- the adjoint of an even side sits one sample off the forms the set holds: "
+                       "odd sides only", who, taps->kh, taps->kw);
+    return PB_OK;
+}
+
 // what both backward calls check before any device work
 int backward_args(pb_ctx *ctx, const char *who, const float *x, const float *grad_out, const float *grad_x, const float *grad_taps,
                   const pb_taps *taps) {
@@ -1242,10 +1251,7 @@ int backward_args(pb_ctx *ctx, const char *who, const float *x, const float *gra
     if (grad_taps && !x) return pb_fail(ctx, PB_ERR_BADARG, "%s: the tap gradient needs x", who);
     if ((grad_x && (grad_x == grad_out || grad_x == x)) || (grad_taps && (grad_taps == grad_out || grad_taps == x || grad_taps == grad_x)))
         return pb_fail(ctx, PB_ERR_BADARG, "%s: an output aliases an input", who);
-    if (taps && (!(taps->kh & 1) || !(taps->kw & 1)))
-        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "%s: a %d x %d kernel -- the adjoint of an even side sits one sample off the forms the set holds: "
-                       "odd sides only", who, taps->kh, taps->kw);
-    return PB_OK;
+    return odd_sides_only(ctx, who, taps);
 }
 
 }  // namespace
@@ -1530,6 +1536,40 @@ int pb_compute_polynomial_taps_backward(pb_ctx *ctx, const float *x, const float
         return run_polynomial(ctx, ga, grad_out, PB_F32, grad_out, arecs, alpha, beta, boundary, t1, t2, grad_x, PB_F32, 0);
     }
     return PB_OK;
+}
+
+int pb_compute_polynomial_taps_params_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_params, int B, int C, int H,
+                                               int W, const pb_taps *taps, float alpha, float beta, int boundary) {
+    static const char *who = "pb_compute_polynomial_taps_params_backward";
+    (void)alpha; (void)beta;                                // (the polynomial is linear in both: neither gradient depends on them)
+    int rc = check_shape(ctx, PB_F32, B, C, H, W);
+    if (rc) return rc;
+    if (!x || !grad_out || !grad_params) return pb_fail(ctx, PB_ERR_BADARG, "%s: x, grad_out or grad_params is null", who);
+    if (static_cast<const void *>(grad_params) == x || static_cast<const void *>(grad_params) == grad_out)
+        return pb_fail(ctx, PB_ERR_BADARG, "%s: an output aliases an input", who);
+    rc = odd_sides_only(ctx, who, taps);
+    if (rc) return rc;
+    if (B > 65535) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "%s: %d images (the kernels' grids take up to 65535)", who, B);
+    Geometry g; const pb_blur_info *recs = nullptr;
+    rc = taps_geometry(ctx, taps, B, C, H, W, boundary, true, false, &g, &recs);
+    if (rc) return rc;
+    PB_HIP(hipSetDevice(ctx->device));
+    g.pp = W; g.pplane = g.HW;
+    // the detail images u1 = x - K x, u2 = u1 - K u1, u3 = u2 - K u2: three explicit Horner steps with scale -1, coef 1 and the
+    // step's own input as its x operand, under the call's boundary -- K is the forward's own operator.  u3 overwrites u1
+    const size_t bytes = sizeof(float) * g.P * g.HW;
+    float *ua = static_cast<float *>(pb_scratch(ctx, "ppg.u1", bytes)), *ub = static_cast<float *>(pb_scratch(ctx, "ppg.u2", bytes));
+    if (!ua || !ub) return PB_ERR_NOMEM;
+    ConvPass p = base_pass(g, recs, boundary);
+    p.scale = -1.f; p.coef = 1.f;
+    const float *src[3] = {x, ua, ub};
+    float *dst[3] = {ua, ub, ua};
+    for (int s = 0; s < 3; ++s) {
+        set_in_padded(p, g, src[s]); set_x_padded(p, g, src[s]); set_out_padded(p, g, dst[s]);
+        rc = taps_pass(ctx, g, p);
+        if (rc) return rc;
+    }
+    return pb_launch_poly_param_reduce(ctx, grad_out, ub, ua, grad_params, B, (long)C * g.HW);
 }
 
 int pb_edgetaper_taps_backward(pb_ctx *ctx, const float *x, const float *grad_out, float *grad_x, float *grad_taps, int B, int C, int H,

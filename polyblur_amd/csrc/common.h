@@ -361,6 +361,12 @@ int pb_launch_tap_gradient(pb_ctx *ctx, const float *u, const float *v, int B, i
                            float scale, int accumulate, float *grad);
 int pb_tap_gradient_groups(int B, int C, int H, int W);
 
+// the gradient of the polynomial with respect to alpha and beta (poly_param_grad.hip): grad_params[b] =
+// (1/2 sum G (u2 - u3), sum G u3) over the n = C * H * W samples of image b, u2 and u3 the second and third detail image of x
+// (api.hip forms them).  B up to 65535.  Partials in the scratch "ppg.partial": 2 * B * pb_poly_param_groups doubles
+int pb_launch_poly_param_reduce(pb_ctx *ctx, const float *grad_out, const float *u2, const float *u3, float *grad_params, int B, long n);
+int pb_poly_param_groups(int B, long n);
+
 // the backward of an edgetaper blend (edgetaper_grad.hip).  TaperAcorr: where the forward reads the kernel's
 // two autocorrelations -- image b's at acy + b * stride and acx + b * stride, nlag lags stored (25 in a record, 49 in a table).
 struct TaperAcorr { const float *acy, *acx; long stride; int nlag; };

@@ -11,7 +11,7 @@
 //   est_dir_argmax     per direction the sample of largest |cos t gx - sin t gy|: (value, linear index) per thread, wave,
 //   est_argmax_reduce  workgroup, image -- larger |value| first, then the lower index, at every level; no atomics
 //   est_param_grad     one workgroup per image: the scalar chain from the forward's record, the 2 (n_angles + 1) row / column
-//                      coefficients, d lo and d hi
+//                      coefficients, d lo and d hi; where asked, d loss / d (c, b) of the affine model as well
 //   est_grad_scatter   every output sample sums its row and column terms with the impulse response of the spectral
 //                      derivative in closed form, adds its share of d lo / d hi, divides by C
 //
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(EG_NT) void est_param_grad(const pb_blur_info *__re
                                                         const EgSel *__restrict__ sel, const float *__restrict__ gray,
                                                         const uint2 *__restrict__ counts, EgCoef *__restrict__ coefs, int H, int W,
                                                         int bpi_counts, int n_angles, int n_interp, float c, float bq, int ksize,
-                                                        PbAngleTable ang) {
+                                                        PbAngleTable ang, float *__restrict__ grad_cb) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const pb_blur_info *info = infos + b;
     const int na = n_angles + 1;
@@ -291,12 +291,16 @@ __global__ __launch_bounds__(EG_NT) void est_param_grad(const pb_blur_info *__re
         // (sigma, rho) -> the two interpolated magnitudes (blur_estimation.py:171-185; torch's clamp passes the gradient on
         // the closed interval)
         const double cc = (double)c * c;
-        double dm[2];
+        double dm[2], d_c = 0.0, d_b = 0.0;
         for (int e = 0; e < 2; ++e) {
             const double m = s_m[e], den = m * m + PbVariance<double>::eps;
             const double dv = s_pass[e] ? dpar[e] / (2.0 * s_par[e]) : 0.0;
             dm[e] = dv * (-2.0 * cc * m) / (den * den);
+            // the model's own parameters: a clamped variance passes nothing on, dv is exactly 0
+            d_c += dv * pb_variance_dc(m, (double)c);
+            d_b += dv * pb_variance_db((double)bq);
         }
+        if (grad_cb) { grad_cb[2 * b] = (float)d_c; grad_cb[2 * b + 1] = (float)d_b; }
         // interpolation and maxima: d mags = W^T d interp; the maxima were divided by the range
         for (int k = 0; k < PB_MAX_ANGLES; ++k) {
             float cx = 0.f, cy = 0.f;
@@ -383,24 +387,26 @@ static int eg_blocks(long work, int B) {
 
 }  // namespace
 
-extern "C" int pb_estimate_blur_backward(pb_ctx *ctx, const float *in, int B, int C, int H, int W, const pb_options *opt,
-                                         const pb_blur_info *dev_info, const float *grad_kernel, const float *grad_sigma_rho,
-                                         int ker_size, float *grad_in) {
-    if (!ctx) return PB_ERR_BADARG;
-    if (!in || !opt || !dev_info || !grad_in || (!grad_kernel && !grad_sigma_rho))
-        return pb_fail(ctx, PB_ERR_BADARG, "pb_estimate_blur_backward: null argument");
-    if (grad_in == in) return pb_fail(ctx, PB_ERR_BADARG, "pb_estimate_blur_backward: grad_in may not alias in");
+// both entry points: grad_in (the image's gradient) and grad_cb (the model parameters') -- either may be null, not both
+static int estimate_backward(pb_ctx *ctx, const char *who, const float *in, int B, int C, int H, int W, const pb_options *opt,
+                             const pb_blur_info *dev_info, const float *grad_kernel, const float *grad_sigma_rho, int ker_size,
+                             float *grad_in, float *grad_cb) {
+    if (!in || !opt || !dev_info || (!grad_in && !grad_cb) || (!grad_kernel && !grad_sigma_rho))
+        return pb_fail(ctx, PB_ERR_BADARG, "%s: null argument", who);
+    if (grad_in == in) return pb_fail(ctx, PB_ERR_BADARG, "%s: grad_in may not alias in", who);
+    if (grad_cb && (static_cast<const void *>(grad_cb) == in || grad_cb == grad_in || grad_cb == grad_kernel || grad_cb == grad_sigma_rho))
+        return pb_fail(ctx, PB_ERR_BADARG, "%s: grad_cb aliases another argument", who);
     if (B < 1 || C < 1 || H < 2 || W < 2) return pb_fail(ctx, PB_ERR_BADARG, "bad shape (%d,%d,%d,%d)", B, C, H, W);
     if (opt->q != 0.f)
-        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "pb_estimate_blur_backward: q = %g -- the backward of the quantile normalisation is not built (q = 0 only)", (double)opt->q);
+        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "%s: q = %g -- the backward of the quantile normalisation is not built (q = 0 only)", who, (double)opt->q);
     const int ksize = ker_size == 0 ? PB_KSIZE : ker_size;
     if (ksize < 1 || ksize > PB_KSIZE || !(ksize & 1))
-        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "pb_estimate_blur_backward: ker_size %d -- odd sizes up to %d only", ker_size, PB_KSIZE);
-    if (opt->force_theta_deg >= 0.f) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "pb_estimate_blur_backward: not with a forced direction");
+        return pb_fail(ctx, PB_ERR_UNSUPPORTED, "%s: ker_size %d -- odd sizes up to %d only", who, ker_size, PB_KSIZE);
+    if (opt->force_theta_deg >= 0.f) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "%s: not with a forced direction", who);
     if (opt->n_angles < 1 || opt->n_angles + 1 > PB_MAX_ANGLES || opt->n_interpolated_angles < 1 || opt->n_interpolated_angles > PB_MAX_INTERP)
         return pb_fail(ctx, PB_ERR_BADARG, "n_angles / n_interpolated_angles out of range");
     const long HW = (long)H * W;
-    if (HW > 0x7fffffffL - 4) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "pb_estimate_blur_backward: planes of up to 2^31 samples");
+    if (HW > 0x7fffffffL - 4) return pb_fail(ctx, PB_ERR_UNSUPPORTED, "%s: planes of up to 2^31 samples", who);
     if (!pb_fft_length_supported(H) || !pb_fft_length_supported(W))
         return pb_fail(ctx, PB_ERR_UNSUPPORTED, "image %d x %d: lines of up to %d samples are supported", H, W, kMaxLineLength);
     PB_HIP(hipSetDevice(ctx->device));
@@ -440,9 +446,25 @@ extern "C" int pb_estimate_blur_backward(pb_ctx *ctx, const float *in, int B, in
     hipLaunchKernelGGL(est_argmax_reduce, dim3(B), dim3(EG_NT), 0, ctx->stream, apart, sel, bpi, na);
     PB_LAUNCH_CHECK();
     hipLaunchKernelGGL(est_param_grad, dim3(B), dim3(EG_NT), 0, ctx->stream, dev_info, grad_kernel, grad_sigma_rho, wts, sel, gray, counts,
-                       coefs, H, W, bpi, opt->n_angles, opt->n_interpolated_angles, opt->c, opt->b, ksize, ang);
+                       coefs, H, W, bpi, opt->n_angles, opt->n_interpolated_angles, opt->c, opt->b, ksize, ang, grad_cb);
     PB_LAUNCH_CHECK();
+    if (!grad_in) return PB_OK;                              // (the parameters alone: nothing to scatter)
     hipLaunchKernelGGL(est_grad_scatter, dim3(bpi, B), dim3(EG_NT), 0, ctx->stream, gray, coefs, grad_in, C, H, W, na);
     PB_LAUNCH_CHECK();
     return PB_OK;
+}
+
+extern "C" int pb_estimate_blur_backward(pb_ctx *ctx, const float *in, int B, int C, int H, int W, const pb_options *opt,
+                                         const pb_blur_info *dev_info, const float *grad_kernel, const float *grad_sigma_rho,
+                                         int ker_size, float *grad_in) {
+    if (!ctx) return PB_ERR_BADARG;
+    if (!grad_in) return pb_fail(ctx, PB_ERR_BADARG, "pb_estimate_blur_backward: null argument");
+    return estimate_backward(ctx, "pb_estimate_blur_backward", in, B, C, H, W, opt, dev_info, grad_kernel, grad_sigma_rho, ker_size, grad_in, nullptr);
+}
+
+extern "C" int pb_estimate_blur_params_backward(pb_ctx *ctx, const float *in, int B, int C, int H, int W, const pb_options *opt,
+                                                const pb_blur_info *dev_info, const float *grad_kernel, const float *grad_sigma_rho,
+                                                int ker_size, float *grad_in, float *grad_cb) {
+    if (!ctx) return PB_ERR_BADARG;
+    return estimate_backward(ctx, "pb_estimate_blur_params_backward", in, B, C, H, W, opt, dev_info, grad_kernel, grad_sigma_rho, ker_size, grad_in, grad_cb);
 }

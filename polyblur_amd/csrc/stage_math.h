@@ -66,6 +66,10 @@ template <typename T> struct PbVariance;
 template <> struct PbVariance<float> { static constexpr float eps = 1e-8f, lo = 0.09f, hi = 16.0f; };
 template <> struct PbVariance<double> { static constexpr double eps = 1e-8, lo = 0.09, hi = 16.0; };
 template <typename T> __device__ __forceinline__ T pb_variance_of(T m, T cc, T bb) { return cc / (m * m + PbVariance<T>::eps) - bb; }
+// ... and its derivatives with respect to the model's own parameters (est_param_grad): d v / d c = 2 c / (m^2 + eps),
+// d v / d b = -2 b
+template <typename T> __device__ __forceinline__ T pb_variance_dc(T m, T c) { return T(2) * c / (m * m + PbVariance<T>::eps); }
+template <typename T> __device__ __forceinline__ T pb_variance_db(T b) { return T(-2) * b; }
 // whether the clamp passes v on (torch's clamp passes the gradient on the closed interval)
 template <typename T> __device__ __forceinline__ bool pb_variance_passes(T v) { return v >= PbVariance<T>::lo && v <= PbVariance<T>::hi; }
 __device__ __forceinline__ float pb_sigma_of(float v) { return sqrtf(fminf(fmaxf(v, PbVariance<float>::lo), PbVariance<float>::hi)); }

@@ -27,6 +27,12 @@ live code path is the bilateral one, deblurring.py:107-108), ``return_info``, ``
 A float32 ROCm tensor that requires grad takes the differentiable composition (``_blind_under_grad``): estimation, non-blind
 step, ``remove_halo=True``, ``edgetaping=True`` and ``prefiltering=True`` with the bilateral prefilter have the engine's own
 backward passes; the other two prefilters, ``q > 0`` and the patch decomposition are refused before any device work.
+
+Learnable parameters: ``c``, ``b``, ``alpha`` and ``beta`` are Python numbers or one-element tensors (0-dim or of
+shape (1,), float32 or float64, on the CPU or on the image's device).  One that requires grad, with autograd on, takes the same
+composition -- beside a float32 ROCm image, which need not require grad itself -- and its ``.grad`` accumulates over the ``n_iter``
+iterations through autograd (estimation.py, nonblind.py: a tensor's value is read with ``float(t)`` in every stage call, one
+synchronisation each where it lives on a device).  Any other tensor parameter is read once and the call runs as with the number.
 """
 from __future__ import annotations
 
@@ -36,7 +42,8 @@ import numpy as np
 
 from . import _capi as capi
 from ._frontend import (_PREFILTER, CPU_WITH_GRAD, DTYPES, FLOAT32_ONLY, HALO_ONLY, NO_EDGETAPER, NO_QUANTILE, bound_engine,
-                        build_options, check_image_size, is_tensor, refuse_under_grad, staged, wants_grad)
+                        build_options, check_image_size, check_param, is_tensor, param_value, refuse_params, refuse_under_grad, staged,
+                        wants_grad)
 from .edge_aware import edge_aware_filtering
 from .estimation import gaussian_blur_estimation
 from .halo import fourier_gradients
@@ -92,6 +99,12 @@ def polyblur_deblurring(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, sigma_
     """Blind deblurring of ``img`` -- see the module docstring; reference deblurring.py:23-96."""
     start = time()
     array = isinstance(img, np.ndarray)
+    # (learnable parameters, DESIGN.md 4.16: the tensors of c, b, alpha, beta that ask for a gradient -- none: the floats go on)
+    params = dict(c=check_param(c, "c", img), b=check_param(b, "b", img), alpha=check_param(alpha, "alpha", img),
+                  beta=check_param(beta, "beta", img))
+    refuse_params("polyblur_deblurring", img, **params)
+    if all(t is None for t in params.values()):
+        params = None
     if array:
         # utils.to_tensor + unsqueeze (deblurring.py:46-48): HWC -> (1,C,H,W) float32 copy
         if img.ndim == 2:
@@ -110,7 +123,7 @@ def polyblur_deblurring(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, sigma_
             raise ValueError("expected a (B,C,H,W) tensor, got shape %r" % (tuple(img.shape),))
         if img.dtype not in (torch.float32, torch.float16):
             raise TypeError("tensor dtype must be float32 or float16 (the reference is float32-only)")
-        if wants_grad(img):
+        if wants_grad(img) or params:
             return _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_interpolated_angles, remove_halo, edgetaping,
                                      prefiltering, discard_saturation, multichannel_kernel, method, support, return_info, temporaries,
                                      prefilter, sigma_s, sigma_r)
@@ -118,6 +131,7 @@ def polyblur_deblurring(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, sigma_
     check_image_size(*x.shape[-2:])
     if temporaries == "fp16" and dt != np.float16:
         raise ValueError("temporaries='fp16' applies to float16 images only")
+    c, b, alpha, beta = param_value(c), param_value(b), param_value(alpha), param_value(beta)     # (tensors that ask for nothing: numbers)
     opts = build_options(x.shape[1], n_iter, c, b, alpha, beta, sigma_r, sigma_s, ker_size, q, n_angles,
                          n_interpolated_angles, remove_halo, edgetaping, prefiltering, discard_saturation,
                          multichannel_kernel, method, support, prefilter, temporaries=temporaries)
@@ -358,7 +372,7 @@ class PolyblurDeblurring(_Base):
                 q=0.0, n_angles=6, n_interpolated_angles=30, remove_halo=False, edgetaping=False, prefiltering=False,
                 discard_saturation=False, multichannel_kernel=False, method='fft', device=None, **extras):
         if self.patch_decomposition:
-            if wants_grad(images):
+            if wants_grad(images) or any(check_param(t, n, images) is not None for n, t in (("c", c), ("b", b), ("alpha", alpha), ("beta", beta))):
                 refuse_under_grad("PolyblurDeblurring(patch_decomposition=True)", "the patch extraction and the windowed overlap-add "
                                   "(pb_extract_patches, pb_overlap_add) are not differentiated")
             return _patchwise_deblurring(images, self.patch_size, self.patch_overlap, self.batch_size,

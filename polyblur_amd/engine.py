@@ -330,6 +330,14 @@ class Engine:
         self._check(self.lib.pb_compute_polynomial_taps_backward(self.ctx, x_ptr, grad_out_ptr, grad_x_ptr, grad_taps_ptr, B, Cc, H, W,
                                                                  ks.handle, float(alpha), float(beta), int(boundary)))
 
+    def compute_polynomial_taps_params_backward_ptr(self, x_ptr: int, grad_out_ptr: int, grad_params_ptr: int, shape, ks: KernelSet, alpha,
+                                                    beta, boundary=capi.PB_WRAP):
+        """(d / d alpha, d / d beta) of compute_polynomial(not_symmetric=False) per image into the (B,2) float32 device array at
+        grad_params_ptr (pb_compute_polynomial_taps_params_backward)"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_compute_polynomial_taps_params_backward(self.ctx, x_ptr, grad_out_ptr, grad_params_ptr, B, Cc, H, W,
+                                                                        ks.handle, float(alpha), float(beta), int(boundary)))
+
     def compute_polynomial_phase_taps_backward_ptr(self, x_ptr, grad_out_ptr: int, grad_x_ptr, grad_taps_ptr, shape, ks: KernelSet, alpha,
                                                    beta):
         """the same for compute_polynomial(method='fft', not_symmetric=True); kernel sides even or odd
@@ -358,6 +366,14 @@ class Engine:
         B, Cc, H, W = (int(v) for v in shape)
         self._check(self.lib.pb_estimate_blur_backward(self.ctx, in_ptr, B, Cc, H, W, C.byref(opts), info_ptr, grad_kernel_ptr,
                                                        grad_sigma_rho_ptr, int(ker_size), grad_in_ptr))
+
+    def estimate_blur_params_backward_ptr(self, in_ptr: int, shape, opts: capi.pb_options, info_ptr: int, grad_kernel_ptr,
+                                          grad_sigma_rho_ptr, ker_size: int, grad_in_ptr, grad_cb_ptr):
+        """estimate_blur_backward_ptr with one more output: d loss / d (c, b) per image into the (B,2) float32 device array at
+        grad_cb_ptr; grad_in_ptr or grad_cb_ptr may be None, not both (pb_estimate_blur_params_backward)"""
+        B, Cc, H, W = (int(v) for v in shape)
+        self._check(self.lib.pb_estimate_blur_params_backward(self.ctx, in_ptr, B, Cc, H, W, C.byref(opts), info_ptr, grad_kernel_ptr,
+                                                              grad_sigma_rho_ptr, int(ker_size), grad_in_ptr, grad_cb_ptr))
 
     def convolve2d_taps(self, x: np.ndarray, ks: KernelSet, boundary=capi.PB_ZERO) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)

@@ -23,14 +23,23 @@ the affine model, the cubic interpolation, the directional maxima (to the arg-ma
 and the min / max normalisation (shared among ties, as torch.amin / amax).  Under grad: float32 ROCm tensors and ``q=0`` only
 (``q=0`` is what the blind driver defaults to; the backward of torch.quantile is not built) -- NotImplementedError before any
 device work otherwise.  No double backward.  Without grad nothing is recorded and ``q`` is free.
+
+Learnable parameters: ``c`` and ``b`` of the affine model sigma^2 = c^2 / (m^2 + 1e-8) - b^2 are Python numbers or
+one-element tensors (0-dim or of shape (1,), float32 or float64, on the CPU or on the image's device; more elements: ValueError).
+A tensor's value is read once per call with ``float(t)`` -- one synchronisation where it lives on a device -- and the forward is the
+forward with that float, bit for bit.  Where autograd is on and a parameter requires grad the result has a ``grad_fn`` -- a parameter
+alone is enough: the calibration case, an image that is data, computes no image gradient -- and its ``.grad`` comes from the same
+backward call (pb_estimate_blur_params_backward: d c = sum_e dv_e 2 c / (m_e^2 + 1e-8), d b = -2 b sum_e dv_e per image; a clamped
+sigma^2 or rho^2 contributes exactly 0), summed over the images in index order in float64, in the parameter's shape, dtype and
+device.  Such a parameter beside an image that is not a float32 ROCm tensor: NotImplementedError before any device work.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import _capi as capi
-from ._frontend import (CPU_WITH_GRAD, DTYPES, FLOAT32_ONLY, NO_QUANTILE, build_options, check_image, check_image_size, host_array,
-                        is_tensor, refuse_under_grad, staged, wants_grad)
+from ._frontend import (CPU_WITH_GRAD, DTYPES, FLOAT32_ONLY, NO_QUANTILE, build_options, check_image, check_image_size, check_param,
+                        host_array, is_tensor, param_value, refuse_params, refuse_under_grad, staged, wants_grad)
 
 _F32 = capi.INFO_DTYPE.itemsize // 4                          # a record in float32 words
 _OFF = {name: capi.INFO_DTYPE.fields[name][1] // 4 for name in ("kernel", "sigma", "rho", "theta")}
@@ -78,7 +87,9 @@ def gaussian_blur_estimation(imgc, q=0.0001, n_angles=6, n_interpolated_angles=3
             (ker_size % 2 == 0 or ker_size > capi.PB_KSIZE):
         raise NotImplementedError("gaussian_blur_estimation returns odd kernels of 3 to 25 taps a side: an even grid's placement depends on "
                                   "the method, which this function does not take, and larger kernels do not live in the estimation record")
-    want_grad = wants_grad(imgc)
+    params = (check_param(c, "c", imgc), check_param(b, "b", imgc))
+    refuse_params("gaussian_blur_estimation", imgc, c=params[0], b=params[1])
+    want_grad = wants_grad(imgc, *params)
     if want_grad:
         what = "gaussian_blur_estimation"
         if dt == np.float16:
@@ -87,12 +98,17 @@ def gaussian_blur_estimation(imgc, q=0.0001, n_angles=6, n_interpolated_angles=3
             refuse_under_grad(what + "(q=%g)" % q, NO_QUANTILE)
         if not imgc.is_cuda:
             refuse_under_grad(what, CPU_WITH_GRAD % "imgc")
+    c, b = param_value(c), param_value(b)                     # (a device parameter is read here, behind the refusals under grad)
     opts = build_options(shape[1], 1, c, b, 2, 3, 0.8, 2.0, ker_size, q, n_angles, n_interpolated_angles, False, False, False,
                          discard_saturation, multichannel, "fft", "full", "bilateral")
     _check_grid(thetas, np.linspace(0, 180, n_angles + 1), "thetas")
     _check_grid(interpolated_thetas, np.arange(n_interpolated_angles) * (180 / n_interpolated_angles), "interpolated_thetas")
     check_image_size(*shape[-2:])
     k = int(ker_size)
+    if params[0] is not None or params[1] is not None:
+        from ._autograd import EstimationParamsFunction
+        return EstimationParamsFunction.apply(imgc, params[0], params[1], opts, k, bool(return_2d_filters), lambda x: _records(x, dt, opts),
+                                              (lambda rec: _kernel_of(rec, k)) if return_2d_filters else _params_of)
     if want_grad:
         from ._autograd import EstimationFunction
         return EstimationFunction.apply(imgc, opts, k, bool(return_2d_filters), lambda x: _records(x, dt, opts),

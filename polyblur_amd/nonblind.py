@@ -27,7 +27,8 @@ such bins near Nyquist) the phase of that filter is noise, in the reference as m
 
 Gradients (the reference's README: "fully differentiable"): ``convolve2d``, ``compute_polynomial`` and
 ``inverse_filtering_rank3`` return a tensor with a ``grad_fn`` when autograd is enabled and ``img`` or ``kernel`` is a tensor
-that requires grad -- with respect to the image and to the taps (not to alpha and b; no double backward).  The backward passes
+that requires grad -- with respect to the image and to the taps, and to ``alpha`` and ``b`` where they are tensors (below; no
+double backward).  The backward passes
 are the engine's too (pb_convolve2d_taps_backward, pb_compute_polynomial_taps_backward); the pad, crop and clamp of
 ``inverse_filtering_rank3`` are then torch's own ops -- the replicate pad composed of slices, expand and cat, whose backward is
 an ordered sum where F.pad's adds with float atomics.  ``remove_halo=True`` under grad is ``halo_masking`` (halo.py; DESIGN.md
@@ -46,6 +47,17 @@ sides even or odd: nothing in that adjoint is centred.  Under grad: float32 ROCm
 backward takes odd sides and is not wired in front of the pure-phase filter), padded sides the engine holds in LDS.  With no ROCm tensor among the operands the refusal is the one it has always been ("the pure-phase filter is
 not differentiated").
 
+Learnable parameters: ``alpha`` and ``b`` of ``compute_polynomial`` and ``inverse_filtering_rank3`` are Python
+numbers or one-element tensors (0-dim or of shape (1,), float32 or float64, on the CPU or on the image's device; more elements:
+ValueError).  A tensor's value is read once per call with ``float(t)`` -- the launch plan sizes window halos from the coefficients
+on the host, so a parameter that lives on a device costs one synchronisation -- and the forward is the forward with that float,
+bit for bit.  Where autograd is on and a parameter requires grad the result has a ``grad_fn`` -- a parameter alone is enough, and
+then no image or kernel gradient is computed -- and its ``.grad`` is the engine's (pb_compute_polynomial_taps_params_backward:
+d/d alpha = 1/2 <G, K (1 - K)^2 x>, d/d b = <G, (1 - K)^3 x> from the detail images, per image), summed over the images in index
+order in float64, in the parameter's shape, dtype and device.  Refused before any device work: such a parameter beside an image
+that is not a float32 ROCm tensor, and on the pure-phase path (``not_symmetric=True``, ``inverse_filtering_nonsymmetric``), where
+these gradients are not built.
+
 The arithmetic is the HIP engine's (include/polyblur_hip.h: pb_taps_create and the *_taps calls); nothing runs on the CPU.
 """
 from __future__ import annotations
@@ -53,8 +65,9 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi as capi
-from ._frontend import (CPU_WITH_GRAD, DTYPES, FLOAT32_ONLY, HALO_ONLY, NO_EDGETAPER, check_grad_img, check_image, check_image_size,
-                        check_phase_sides, host_array, is_rocm_float32, is_tensor, refuse_under_grad, staged, wants_grad)
+from ._frontend import (CPU_WITH_GRAD, DTYPES, FLOAT32_ONLY, HALO_ONLY, NO_EDGETAPER, NO_PHASE_PARAMS, check_grad_img, check_image,
+                        check_image_size, check_param, check_phase_sides, host_array, is_rocm_float32, is_tensor, param_value,
+                        refuse_params, refuse_under_grad, staged, wants_grad)
 from .halo import halo_masking
 
 _BOUNDARY = {"fft": capi.PB_WRAP, "direct": capi.PB_ZERO}
@@ -122,7 +135,11 @@ def _check_grad(img, kernel, what, even_ok=False):
         refuse_under_grad(what, "img is a CPU tensor or a NumPy array -- gradients are built for ROCm tensors only")
 
 
-def _apply_taps_function(img, kernel, taps, eshape, bnd, poly, call, correlate=False):
+def _apply_taps_function(img, kernel, taps, eshape, bnd, poly, call, correlate=False, params=(None, None)):
+    """params: the tensors of (alpha, b) that ask for a gradient (check_param), None for the others"""
+    if params[0] is not None or params[1] is not None:
+        from ._autograd import TapsParamsFunction
+        return TapsParamsFunction.apply(img, kernel if is_tensor(kernel) else None, params[0], params[1], taps, eshape, bnd, poly, correlate, call)
     from ._autograd import TapsFunction
     return TapsFunction.apply(img, kernel if is_tensor(kernel) else None, taps, eshape, bnd, poly, correlate, call)
 
@@ -201,11 +218,13 @@ def inverse_filtering_rank3(img, kernel, alpha=2, b=4, correlate=False, remove_h
     crop -> [halo masking] -> clamp.  ``grad_img``: (grad_x, grad_y) of the original image, or None for the gradients of
     the (tapered) image itself."""
     shape, dt = check_image(img, allow_half=True)
+    params = (check_param(alpha, "alpha", img), check_param(b, "b", img))
+    refuse_params("inverse_filtering_rank3", img, alpha=params[0], b=params[1])
     taps, eshape = _check_kernel(kernel, method, shape, pad_domain=True, circular_only=bool(do_edgetaper),
                                     correlate=bool(correlate))
     halo_planes = tuple(grad_img) if remove_halo and isinstance(grad_img, (tuple, list)) and len(grad_img) == 2 else ()
     bnd = _BOUNDARY[method]
-    if wants_grad(img, kernel, *halo_planes):
+    if wants_grad(img, kernel, *halo_planes, *params):
         # (the stage's device check first: its reason names the stage; the kernel's own checks follow: _check_grad)
         if remove_halo and not all(is_rocm_float32(t) for t in (img,) + halo_planes):
             refuse_under_grad("inverse_filtering_rank3(remove_halo=True)", HALO_ONLY)
@@ -218,6 +237,7 @@ def inverse_filtering_rank3(img, kernel, alpha=2, b=4, correlate=False, remove_h
             if grad_img is not None:
                 check_grad_img(grad_img, shape)
         from ._autograd import replicate_pad
+        alpha, b = param_value(alpha), param_value(b)         # (every refusal has passed: a device parameter is read now)
         pad = taps.shape[-1] // 2
         xp = replicate_pad(img, pad)                          # (the polynomial's domain: the engine's shape with the padded sides)
         pshape = eshape[:2] + tuple(xp.shape[-2:])
@@ -226,12 +246,14 @@ def inverse_filtering_rank3(img, kernel, alpha=2, b=4, correlate=False, remove_h
             if remove_halo:
                 img = xp[..., pad:-pad, pad:-pad]             # (the mask's image is the tapered one: deblurring.py:236-238)
         y = _apply_taps_function(xp, kernel, taps, pshape, bnd, (alpha, b),
-                                 lambda eng, i, o, ex, ks: eng.compute_polynomial_taps_ptr(i, o[0], pshape, ks, alpha, b, bnd, False), bool(correlate))
+                                 lambda eng, i, o, ex, ks: eng.compute_polynomial_taps_ptr(i, o[0], pshape, ks, alpha, b, bnd, False), bool(correlate),
+                                 params)
         y = y[..., pad:-pad, pad:-pad]
         if remove_halo:
             y = halo_masking(img, y, grad_img)                # (grad_img None: fourier_gradients(img), inside the graph)
         return y.clamp(0.0, 1.0)
     dtype = DTYPES[dt]
+    alpha, b = param_value(alpha), param_value(b)
     return _chain(img, dt, shape, taps, remove_halo, grad_img,
                   lambda eng, i, o, ex, ks: eng.inverse_filter_taps_ptr(i, o[0], dtype, eshape, ks, alpha, b, bnd, bool(do_edgetaper),
                                                                         bool(remove_halo), *(ex or _OWN)))
@@ -244,22 +266,30 @@ def compute_polynomial(img, kernel, alpha, b, method='fft', not_symmetric=False)
     ignores it; here that is a ValueError.  Where |K| falls to fp32 roundoff the filter's phase is noise (see the module).
     Differentiable with respect to ``img`` and ``kernel``, with the flag too (float32 ROCm tensors)."""
     shape, dt = check_image(img, allow_half=False)
+    params = (check_param(alpha, "alpha", img), check_param(b, "b", img))
+    if not_symmetric and (params[0] is not None or params[1] is not None):
+        refuse_under_grad("compute_polynomial(not_symmetric=True)", NO_PHASE_PARAMS)
+    refuse_params("compute_polynomial", img, alpha=params[0], b=params[1])
     taps, eshape = _check_kernel(kernel, method, shape, pad_domain=False, circular_only=False)
     if not_symmetric and method != "fft":
         raise ValueError("not_symmetric=True is the pure-phase filter of method='fft' (the reference's direct form ignores the flag)")
     bnd = _BOUNDARY[method]
+    # (alpha and b are read by the call when it runs: by then they are the numbers param_value gives, after every refusal)
     call = lambda eng, i, o, ex, ks: eng.compute_polynomial_taps_ptr(i, o[0], eshape, ks, alpha, b, bnd, bool(not_symmetric))
-    if wants_grad(img, kernel):
+    if wants_grad(img, kernel, *params):
         if not_symmetric:
             if not _any_rocm(img, kernel):
                 refuse_under_grad("compute_polynomial(not_symmetric=True)", _NO_PHASE)
             _check_grad(img, kernel, "compute_polynomial(not_symmetric=True)", even_ok=True)
             check_phase_sides(shape[2], shape[3])
+            alpha, b = param_value(alpha), param_value(b)
             return _apply_phase_function(img, kernel, taps, eshape, alpha, b)
         _check_grad(img, kernel, "compute_polynomial")
-        return _apply_taps_function(img, kernel, taps, eshape, bnd, (alpha, b), call)
+        alpha, b = param_value(alpha), param_value(b)
+        return _apply_taps_function(img, kernel, taps, eshape, bnd, (alpha, b), call, params=params)
     if not_symmetric:
         check_phase_sides(shape[2], shape[3])
+    alpha, b = param_value(alpha), param_value(b)
     return _run(img, dt, taps, call)
 
 
@@ -270,6 +300,8 @@ def inverse_filtering_nonsymmetric(img, kernel, alpha=2, b=4, correlate=False, r
     -> clamp.  float32 or float16 images.  Where |K| falls to fp32 roundoff the filter's phase is noise (see the module).
     Differentiable with respect to ``img``, ``kernel`` and ``grad_img`` (float32 ROCm tensors, no ``do_edgetaper``)."""
     shape, dt = check_image(img, allow_half=True)
+    if check_param(alpha, "alpha", img) is not None or check_param(b, "b", img) is not None:
+        refuse_under_grad("inverse_filtering_nonsymmetric", NO_PHASE_PARAMS)
     taps, eshape = _check_kernel(kernel, "fft", shape, pad_domain=True, circular_only=bool(do_edgetaper),
                                     correlate=bool(correlate))
     halo_planes = tuple(grad_img) if remove_halo and isinstance(grad_img, (tuple, list)) and len(grad_img) == 2 else ()
@@ -290,6 +322,7 @@ def inverse_filtering_nonsymmetric(img, kernel, alpha=2, b=4, correlate=False, r
             if grad_img is not None:
                 check_grad_img(grad_img, shape)
         from ._autograd import replicate_pad
+        alpha, b = param_value(alpha), param_value(b)
         xp = replicate_pad(img, pad)
         y = _apply_phase_function(xp, kernel, taps, eshape[:2] + tuple(xp.shape[-2:]), alpha, b, bool(correlate))
         y = y[..., pad:-pad, pad:-pad]
@@ -298,6 +331,7 @@ def inverse_filtering_nonsymmetric(img, kernel, alpha=2, b=4, correlate=False, r
         return y.clamp(0.0, 1.0)
     check_phase_sides(shape[2] + 2 * pad, shape[3] + 2 * pad)
     dtype = DTYPES[dt]
+    alpha, b = param_value(alpha), param_value(b)
     return _chain(img, dt, shape, taps, remove_halo, grad_img,
                   lambda eng, i, o, ex, ks: eng.inverse_filter_phase_taps_ptr(i, o[0], dtype, eshape, ks, alpha, b, bool(do_edgetaper),
                                                                               bool(remove_halo), *(ex or _OWN)))
