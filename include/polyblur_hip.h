@@ -538,6 +538,33 @@ int pb_overlap_add(pb_ctx *ctx, const void *patches, void *out, int dtype, int B
                    int ph, int pw, int step_h, int step_w, int n_i, int n_j, int pad_top, int pad_left,
                    const float *dev_win_y, const float *dev_win_x);
 
+/* pb_extract_patches_backward: the backward of pb_extract_patches with respect to the image, over ALL n_i*n_j patches (no first /
+ * count).  grad_patches ([n*B + b, c, y, x], the upstream gradient of the patches) and grad_img (B,C,H,W) are float32 DEVICE
+ * memory; grad_img is written, not accumulated, and may not alias grad_patches.  grad_img[b,c,Y,X] is the sum of
+ * grad_patches[n*B + b, c, py - i0(n), px - j0(n)] over every padded position (py, px) that clamps to (Y, X) and every patch that
+ * holds it: one position inside, a run of pad + 1 on an edge, a rectangle in a corner.  The lattice arguments are the forward's;
+ * ph, pw < 2, a step < 1, a lattice without a patch or a null pointer is PB_ERR_BADARG before any launch.  Three launches: the
+ * cover gathered into a padded plane set, the fold of the padded rows, the fold of the padded columns -- no thread adds more than
+ * a pad's run or a cover's patches.  Scratch: one padded plane set of new_h x new_w ("patchg.P") and one of H x new_w
+ * ("patchg.R").  fp32 sums in an order the shape alone fixes, no float atomics: the same call gives the same bits.  Asynchronous
+ * on the context's stream.                                                                                                        */
+int pb_extract_patches_backward(pb_ctx *ctx, const float *grad_patches, float *grad_img, int B, int C, int H, int W,
+                                int ph, int pw, int step_h, int step_w, int n_i, int n_j, int pad_top, int pad_left);
+
+/* pb_overlap_add_backward: the backward of pb_overlap_add with respect to the patches (no gradient with respect to the window).
+ * patches (the forward's input) and grad_patches are [n*B + b, c, y, x], grad_out (the upstream gradient of out) is (B,C,H,W), all
+ * float32 DEVICE memory; grad_patches is written everywhere, zeros included, and may alias no input.  With num, den the forward's
+ * cover sums at the image sample (Y, X) of a patch element and v = num / (den + 1e-8),
+ *   grad_patches[n*B + b, c, y, x] = win_y[y] win_x[x] m grad_out[b,c,Y,X] / (den + 1e-8),   m = [0 <= v <= 1],
+ * and exactly 0 for the elements in the cropped pad.  The mask is inclusive at both ends (torch.clamp's gradient), and v is formed
+ * again from `patches` by the forward's own cover function, so m comes from the forward's bits.  Arguments and refusals as
+ * pb_extract_patches_backward's.  Two launches: S = m grad_out / (den + 1e-8) per image sample into a scratch plane set
+ * ("patchg.S"), then the windowed gather per patch element.  Deterministic, no float atomics.  Asynchronous on the context's
+ * stream.                                                                                                                         */
+int pb_overlap_add_backward(pb_ctx *ctx, const float *patches, const float *grad_out, float *grad_patches, int B, int C, int H, int W,
+                            int ph, int pw, int step_h, int step_w, int n_i, int n_j, int pad_top, int pad_left,
+                            const float *dev_win_y, const float *dev_win_x);
+
 /* ---- timing hooks used by bench.py ------------------------------------------------------
  * Runs only the polynomial inner loop (three stencil passes, the SURVEY 8d "inner loop")
  * `reps` times on resident data and returns the average milliseconds per repetition

@@ -20,9 +20,12 @@ from .halo import fourier_gradients, halo_masking  # noqa: F401
 # differentiable, the normalized convolution is forward only
 # (reference filters.py:107-148, domain_transform.py:6-85, deblurring.py:99-110)
 from .edge_aware import bilateral_filter, recursive_filter, normalized_convolution, edge_aware_filtering  # noqa: F401
+# the two ends of the patch decomposition, differentiable (reference deblurring.py:269-340, fix-forward)
+from .patches import image_to_patches, patches_to_image  # noqa: F401
 
 __all__ = ["polyblur_deblurring", "polyblur_deblurring_uint8", "PolyblurDeblurring",
            "inverse_filtering_rank3", "convolve2d", "edgetaper", "compute_polynomial", "inverse_filtering_nonsymmetric",
            "gaussian_blur_estimation", "fourier_gradients", "halo_masking",
-           "bilateral_filter", "recursive_filter", "normalized_convolution", "edge_aware_filtering"]
+           "bilateral_filter", "recursive_filter", "normalized_convolution", "edge_aware_filtering",
+           "image_to_patches", "patches_to_image"]
 __version__ = "0.1.0"

@@ -1,4 +1,4 @@
-"""The package's autograd.Functions (DESIGN.md 4.7-4.9, 4.12-4.14): the forward and backward passes are the engine's, on ROCm float32
+"""The package's autograd.Functions (DESIGN.md 4.7-4.9, 4.12-4.17): the forward and backward passes are the engine's, on ROCm float32
 tensors and torch's current stream; no double backward.  The public functions import this module on first use under grad --
 it is the only one that needs torch at import time -- after every check and refusal of theirs has passed."""
 from __future__ import annotations
@@ -368,3 +368,56 @@ class BilateralFunction(torch.autograd.Function):
         with bound_engine(x) as eng:
             eng.bilateral_backward_ptr(x.data_ptr(), g.data_ptr(), gin.data_ptr(), x.shape, *ctx.pb)
         return gin, None, None, None, None
+
+
+class ExtractPatchesFunction(torch.autograd.Function):
+    """image_to_patches of an even-sized ROCm float32 image: all n_i * n_j patches of the lattice ``grid``
+    (patches.patch_grid) in one call of pb_extract_patches, [n*B + b]; the backward is pb_extract_patches_backward."""
+
+    @staticmethod
+    def forward(ctx, img, grid):
+        x = img.detach().contiguous()
+        B, Cc = x.shape[:2]
+        n_p = grid["n_i"] * grid["n_j"]
+        patches = torch.empty((n_p * B, Cc, grid["ph"], grid["pw"]), dtype=x.dtype, device=x.device)
+        with bound_engine(x) as eng:
+            eng.extract_patches_ptr(x.data_ptr(), patches.data_ptr(), capi.PB_F32, x.shape, grid, 0, n_p)
+        ctx.pb = (tuple(int(v) for v in x.shape), dict(grid))
+        return patches
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_patches):
+        shape, grid = ctx.pb
+        g = _upstream(grad_patches)
+        gin = torch.empty(shape, dtype=torch.float32, device=g.device)
+        with bound_engine(g) as eng:
+            eng.extract_patches_backward_ptr(g.data_ptr(), gin.data_ptr(), shape, grid)
+        return gin, None
+
+
+class OverlapAddFunction(torch.autograd.Function):
+    """patches_to_image of ROCm float32 patches: the one call of pb_overlap_add into an image of ``shape``, with the
+    window tensors wy, wx (patches.windows); the backward is pb_overlap_add_backward, which forms the clamp mask from the patches
+    again with the forward's own cover sum."""
+
+    @staticmethod
+    def forward(ctx, patches, shape, grid, wy, wx):
+        p = patches.detach().contiguous()
+        out = torch.empty(shape, dtype=p.dtype, device=p.device)
+        with bound_engine(p) as eng:
+            eng.overlap_add_ptr(p.data_ptr(), out.data_ptr(), capi.PB_F32, shape, grid, wy.data_ptr(), wx.data_ptr())
+        ctx.save_for_backward(p, wy, wx)
+        ctx.pb = (shape, dict(grid))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        p, wy, wx = ctx.saved_tensors
+        shape, grid = ctx.pb
+        g = _upstream(grad_out)
+        gp = torch.empty_like(p)
+        with bound_engine(p) as eng:
+            eng.overlap_add_backward_ptr(p.data_ptr(), g.data_ptr(), gp.data_ptr(), shape, grid, wy.data_ptr(), wx.data_ptr())
+        return gp, None, None, None, None

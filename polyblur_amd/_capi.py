@@ -44,7 +44,7 @@ SYMBOLS = [
     "pb_edgetaper_taps_backward", "pb_compute_polynomial_taps_params_backward",
     "pb_estimate_blur_backward", "pb_estimate_blur_params_backward",
     "pb_fourier_gradients_backward", "pb_halo_mask_backward", "pb_bilateral_backward",
-    "pb_dt_recursive_filter_backward",
+    "pb_dt_recursive_filter_backward", "pb_extract_patches_backward", "pb_overlap_add_backward",
     "pb_comm_shard", "pb_comm_unique_id", "pb_comm_init", "pb_comm_destroy", "pb_comm_scatter", "pb_comm_gather",
     "pb_comm_deblur_from_root", "pb_comm_plan_steps", "pb_comm_plan", "pb_comm_set_chunk", "pb_comm_default_chunk",
     "pb_comm_plan_steps_chunked", "pb_comm_plan_chunked",
@@ -168,6 +168,8 @@ def load_library():
             "pb_time_inner_loop": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, cf, cf, ci, ci, fp]),
             "pb_extract_patches": (ci, [vp, vp, vp] + [ci] * 15),
             "pb_overlap_add": (ci, [vp, vp, vp] + [ci] * 13 + [vp, vp]),
+            "pb_extract_patches_backward": (ci, [vp, vp, vp] + [ci] * 12),
+            "pb_overlap_add_backward": (ci, [vp, vp, vp, vp] + [ci] * 12 + [vp, vp]),
             "pb_fft_length_supported": (ci, [ci]),
             "pb_make_separable_kernels": (ci, [vp, ci, vp, vp, ci, ci]),
             "pb_body_selection": (ci, [vp, ci, C.POINTER(ci), ci]),

@@ -3,6 +3,7 @@
 //   5x5 bilateral filter             filters.py:107-148
 //   prefilter recombination          deblurring.py:84,88
 #include "stage_math.h"
+#include "patch_cover.h"
 
 int pb_fourier_gradients_impl(pb_ctx *ctx, const float *planes, int P, int H, int W, float *gx, float *gy);
 int pb_bilateral5_sigma_impl(pb_ctx *ctx, const void *in, int in_dtype, void *out, int out_dtype, int P, int H, int W,
@@ -371,7 +372,7 @@ __global__ __launch_bounds__(NT) void extract_patches_kernel(const T *__restrict
 
 // out[b, c, Y, X] = clamp( sum_n restored_n * w / (sum_n w + 1e-8), 0, 1 ) over the patches that cover the
 // (padded) pixel, written straight into the cropped H x W result (deblurring.py:332-340): a gather, so
-// no atomics and no window_sum buffer.
+// no atomics and no window_sum buffer.  The cover sum is patch_cover.h's, shared with pb_overlap_add_backward.
 template <typename T>
 __global__ __launch_bounds__(NT) void overlap_add_kernel(const T *__restrict__ patches, T *__restrict__ out, int B, int C, int H,
                                                          int W, int ph, int pw, int step_h, int step_w, int n_i, int n_j,
@@ -383,24 +384,8 @@ __global__ __launch_bounds__(NT) void overlap_add_kernel(const T *__restrict__ p
         const int Y = (int)(r % H); r /= H;
         const int c = (int)(r % C);
         const int b = (int)(r / C);
-        const int py = Y + pad_top, px = X + pad_left;            // position in the padded image
-        int ki_lo = (py - ph + step_h) / step_h; if (py - ph + 1 <= 0) ki_lo = 0;
-        int kj_lo = (px - pw + step_w) / step_w; if (px - pw + 1 <= 0) kj_lo = 0;
-        const int ki_hi = min(py / step_h, n_i - 1), kj_hi = min(px / step_w, n_j - 1);
-        float num = 0.f, den = 0.f;
-        for (int ki = ki_lo; ki <= ki_hi; ++ki) {
-            const int y = py - ki * step_h;
-            if (y < 0 || y >= ph) continue;
-            for (int kj = kj_lo; kj <= kj_hi; ++kj) {
-                const int x = px - kj * step_w;
-                if (x < 0 || x >= pw) continue;
-                const float w = win_y[y] * win_x[x];
-                const long n = (long)ki * n_j + kj;
-                num += w * pb_ld(patches + (((n * B + b) * C + c) * ph + y) * pw + x);
-                den += w;
-            }
-        }
-        pb_st(out + i, fminf(fmaxf(num / (den + 1e-8f), 0.f), 1.f));
+        const PatchCover cv = patch_cover(patches, B, C, ph, pw, step_h, step_w, n_i, n_j, b, c, Y + pad_top, X + pad_left, win_y, win_x);
+        pb_st(out + i, fminf(fmaxf(patch_cover_value(cv), 0.f), 1.f));
     }
 }
 

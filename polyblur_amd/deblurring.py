@@ -26,7 +26,10 @@ live code path is the bilateral one, deblurring.py:107-108), ``return_info``, ``
 
 A float32 ROCm tensor that requires grad takes the differentiable composition (``_blind_under_grad``): estimation, non-blind
 step, ``remove_halo=True``, ``edgetaping=True`` and ``prefiltering=True`` with the bilateral prefilter have the engine's own
-backward passes; the other two prefilters, ``q > 0`` and the patch decomposition are refused before any device work.
+backward passes; the other two prefilters and ``q > 0`` are refused before any device work.  ``PolyblurDeblurring(patch_decomposition=
+True)`` of such a tensor -- or of a float32 ROCm image beside a learnable parameter -- cuts every patch once, runs this composition
+on groups of ``batch_size`` patches and blends them (patches.py, DESIGN.md 4.17: the extraction and the overlap-add have the engine's
+own backward passes); any other image under grad is refused there.
 
 Learnable parameters: ``c``, ``b``, ``alpha`` and ``beta`` are Python numbers or one-element tensors (0-dim or of
 shape (1,), float32 or float64, on the CPU or on the image's device).  One that requires grad, with autograd on, takes the same
@@ -42,12 +45,13 @@ import numpy as np
 
 from . import _capi as capi
 from ._frontend import (_PREFILTER, CPU_WITH_GRAD, DTYPES, FLOAT32_ONLY, HALO_ONLY, NO_EDGETAPER, NO_QUANTILE, bound_engine,
-                        build_options, check_image_size, check_param, is_tensor, param_value, refuse_params, refuse_under_grad, staged,
+                        build_options, check_image_size, check_param, is_rocm_float32, is_tensor, param_value, refuse_params, refuse_under_grad, staged,
                         wants_grad)
 from .edge_aware import edge_aware_filtering
 from .estimation import gaussian_blur_estimation
 from .halo import fourier_gradients
 from .nonblind import inverse_filtering_rank3
+from .patches import blend, check_lattice, even_part, extract, kaiser_window_periodic, patch_grid  # noqa: F401  (the lattice lives there)
 
 
 def _info_to_dicts(info, n_angles, n_interp):
@@ -146,14 +150,10 @@ def polyblur_deblurring(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, sigma_
     return (out, _info_to_dicts(info, n_angles, n_interpolated_angles)) if return_info else out
 
 
-def _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_interpolated_angles, remove_halo, edgetaping,
-                      prefiltering, discard_saturation, multichannel_kernel, method, support, return_info, temporaries, prefilter,
-                      sigma_s, sigma_r):
-    """polyblur_deblurring of a tensor that requires grad (the reference's README: "fully differentiable"): the blind call as a
-    composition of the package's own differentiable functions -- estimate (estimation.py; DESIGN.md 4.8), with ``prefiltering``
-    the bilateral split (edge_aware.py; 4.12: the step runs on the smooth part and the noise is added back, deblurring.py:80-84),
-    non-blind step (nonblind.py; 4.7) with the halo mask where asked (halo.py; 4.9), clip, n_iter times (deblurring.py:54-90).
-    Every refusal comes before any device work."""
+def _refusals_under_grad(img, n_iter, ker_size, q, remove_halo, edgetaping, prefiltering, method, support, return_info, temporaries,
+                         prefilter):
+    """what polyblur_deblurring refuses of a tensor ``img`` under grad, before any device work (the patch branch asks for the whole
+    image, before it extracts a patch)"""
     import torch
     what = "polyblur_deblurring"
     if remove_halo and not (img.is_cuda and img.dtype == torch.float32):     # (the stage's device check first: its reason names the stage)
@@ -186,6 +186,17 @@ def _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_i
         refuse_under_grad(what, CPU_WITH_GRAD % "img")
     if not (isinstance(n_iter, (int, np.integer)) and n_iter >= 0):
         raise ValueError("n_iter must be an integer >= 0")
+
+
+def _blind_under_grad(img, n_iter, c, b, alpha, beta, ker_size, q, n_angles, n_interpolated_angles, remove_halo, edgetaping,
+                      prefiltering, discard_saturation, multichannel_kernel, method, support, return_info, temporaries, prefilter,
+                      sigma_s, sigma_r):
+    """polyblur_deblurring of a tensor that requires grad (the reference's README: "fully differentiable"): the blind call as a
+    composition of the package's own differentiable functions -- estimate (estimation.py; DESIGN.md 4.8), with ``prefiltering``
+    the bilateral split (edge_aware.py; 4.12: the step runs on the smooth part and the noise is added back, deblurring.py:80-84),
+    non-blind step (nonblind.py; 4.7) with the halo mask where asked (halo.py; 4.9), clip, n_iter times (deblurring.py:54-90).
+    Every refusal comes before any device work."""
+    _refusals_under_grad(img, n_iter, ker_size, q, remove_halo, edgetaping, prefiltering, method, support, return_info, temporaries, prefilter)
     x = img
     # (the halo mask's gradient planes are those of the original input, for every iteration: deblurring.py:61,83)
     grad_img = fourier_gradients(img) if remove_halo and n_iter > 0 else None
@@ -246,29 +257,6 @@ def polyblur_deblurring_uint8(img, n_iter=1, c=0.352, b=0.768, alpha=2, beta=3, 
     return (out, _info_to_dicts(info, n_angles, n_interpolated_angles)) if return_info else out
 
 
-def kaiser_window_periodic(n: int, beta: float = 5.0) -> np.ndarray:
-    """torch.kaiser_window(n, periodic=True, beta) (deblurring.py:352): the symmetric window of
-    length n+1 without its last sample."""
-    if n == 1:
-        return np.ones(1, np.float32)
-    k = np.arange(n, dtype=np.float64)
-    r = 2.0 * k / n - 1.0
-    return (np.i0(beta * np.sqrt(np.maximum(0.0, 1.0 - r * r))) / np.i0(beta)).astype(np.float32)
-
-
-def patch_grid(h: int, w: int, patch_size, overlap: float):
-    """The reference's patch lattice (deblurring.py:281-299): steps, padded size, pads, counts."""
-    ph, pw = patch_size
-    step_h, step_w = int(ph * (1 - overlap)), int(pw * (1 - overlap))
-    new_h = int(np.ceil((h - ph) / step_h) * step_h) + ph
-    new_w = int(np.ceil((w - pw) / step_w) * step_w) + pw
-    pad_top, pad_left = int(np.floor((new_h - h) / 2)), int(np.floor((new_w - w) / 2))
-    n_i = len(range(0, new_h - ph + 1, step_h))
-    n_j = len(range(0, new_w - pw + 1, step_w))
-    return dict(ph=ph, pw=pw, step_h=step_h, step_w=step_w, new_h=new_h, new_w=new_w, pad_top=pad_top,
-                pad_left=pad_left, n_i=n_i, n_j=n_j)
-
-
 def _device_index(device):
     """`device` of PolyblurDeblurring.forward (deblurring.py:322-330: where the patches are deblurred) -> GPU index."""
     if device is None:
@@ -282,8 +270,9 @@ def _device_index(device):
     return d.index if d.index is not None else torch.cuda.current_device()
 
 
-def _patchwise_deblurring(images, patch_size, overlap, batch_size, kwargs, device=None):
-    """PolyblurDeblurring.forward, patch branch (deblurring.py:269-340, fix-forward)."""
+def _patchwise_deblurring(images, patch_size, overlap, batch_size, kwargs, device=None, under_grad=False):
+    """PolyblurDeblurring.forward, patch branch (deblurring.py:269-340, fix-forward).  ``under_grad``: a float32 ROCm image with autograd
+    on and the image or one of c, b, alpha, beta asking for a gradient."""
     import torch
     if not is_tensor(images) or images.dim() != 4:
         raise ValueError("patch decomposition expects a (B,C,H,W) tensor")
@@ -291,15 +280,11 @@ def _patchwise_deblurring(images, patch_size, overlap, batch_size, kwargs, devic
         raise TypeError("tensor dtype must be float32 or float16")
     if kwargs.pop("return_info", False):
         raise TypeError("return_info is not available with patch_decomposition=True (one record set per patch group)")
-    # (the lattice first: a plain error for what the reference's arithmetic leaves without a single patch -- an image shorter than
-    #  patch_size - step along an axis gives new_h < patch_size at deblurring.py:284-285 and an empty I_coords at :294: the
-    #  reference's branch, could it run, would return zeros there)
-    if min(patch_size) < 2 or int(patch_size[0] * (1 - overlap)) < 1 or int(patch_size[1] * (1 - overlap)) < 1:
-        raise ValueError("patch size / overlap incompatible: patches of at least 2x2 with a positive step are needed")
-    g0 = patch_grid(images.shape[-2] // 2 * 2, images.shape[-1] // 2 * 2, patch_size, overlap)
-    if g0["n_i"] < 1 or g0["n_j"] < 1:
-        raise ValueError("image %dx%d is smaller than patch_size - step along an axis: the reference's lattice (deblurring.py:284-295) "
-                         "holds no patch for it -- use a smaller patch_size or patch_decomposition=False" % (images.shape[-2], images.shape[-1]))
+    check_lattice(images.shape[-2], images.shape[-1], patch_size, overlap)        # (the lattice first)
+    if under_grad:                                          # (what the blind call refuses under grad, before a patch is cut)
+        _refusals_under_grad(images, kwargs.get("n_iter", 1), kwargs.get("ker_size", 25), kwargs.get("q", 0.0), kwargs.get("remove_halo", False),
+                             kwargs.get("edgetaping", False), kwargs.get("prefiltering", False), kwargs.get("method", "fft"),
+                             kwargs.get("support", "full"), False, kwargs.get("temporaries", "fp32"), kwargs.get("prefilter", "bilateral"))
     was_cuda = images.is_cuda
     want = _device_index(device)
     if was_cuda:
@@ -308,26 +293,33 @@ def _patchwise_deblurring(images, patch_size, overlap, batch_size, kwargs, devic
             raise ValueError("images live on cuda:%d but device=cuda:%d was requested" % (dev, want))
     else:
         dev = 0 if want is None else want                   # reference: patches.to(device) ... .cpu() (deblurring.py:322-330)
-    x = images if was_cuda else images.to("cuda:%d" % dev)
+    x = even_part(images if was_cuda else images.to("cuda:%d" % dev))       # :273-279 make the size even
     h, w = x.shape[-2:]
-    if h % 2 == 1:                                      # :273-279 make the size even
-        x = x[..., :-1, :]
-        h -= 1
-    if w % 2 == 1:
-        x = x[..., :, :-1]
-        w -= 1
-    x = x.contiguous()
     B, Cc = x.shape[:2]
     g = patch_grid(h, w, patch_size, overlap)
     if g["ph"] < 2 or g["pw"] < 2 or g["step_h"] < 1 or g["step_w"] < 1:
         raise ValueError("patch size / overlap incompatible: patches of at least 2x2 with a positive step are needed")
-    dtype = capi.PB_F32 if x.dtype == torch.float32 else capi.PB_F16
     n_p = g["n_i"] * g["n_j"]
+    group = max(1, int(batch_size))
+    if under_grad:
+        # every patch once -- through ExtractPatchesFunction where the image asks for a gradient, the plain call where it is data --,
+        # the blind call on groups of `batch_size` patches with the caller's c, b, alpha, beta as they are, one overlap-add through
+        # OverlapAddFunction: patches are independent images, so the grouping changes no bit of the output or of the image's gradient
+        # A learnable parameter goes to the groups as its float64 copy: a group's gradient is the float64 sum of its images' float32
+        # rows (_autograd._param_grad), autograd adds the groups and the iterations in float64 -- sums of a few hundred float32
+        # values, which float64 holds exactly -- and the one rounding to the parameter's dtype comes last: the grouping does not
+        # reach the parameter's gradient either.
+        for name in ("c", "b", "alpha", "beta"):
+            if check_param(kwargs.get(name), name, images) is not None:
+                kwargs[name] = kwargs[name].double()
+        patches = extract(x, g)
+        restored = [polyblur_deblurring(patches[first * B:min(first + group, n_p) * B], **kwargs) for first in range(0, n_p, group)]
+        return blend(torch.cat(restored) if len(restored) > 1 else restored[0].contiguous(), x.shape, g)
+    dtype = capi.PB_F32 if x.dtype == torch.float32 else capi.PB_F16
     wy = torch.from_numpy(kaiser_window_periodic(g["ph"])).to(x.device)
     wx = torch.from_numpy(kaiser_window_periodic(g["pw"])).to(x.device)
     restored = torch.empty((n_p * B, Cc, g["ph"], g["pw"]), dtype=x.dtype, device=x.device)
     with bound_engine(x) as eng:
-        group = max(1, int(batch_size))
         for first in range(0, n_p, group):                       # :310 groups of `batch_size` patches
             count = min(group, n_p - first)
             patches = torch.empty((count * B, Cc, g["ph"], g["pw"]), dtype=x.dtype, device=x.device)
@@ -372,7 +364,8 @@ class PolyblurDeblurring(_Base):
                 q=0.0, n_angles=6, n_interpolated_angles=30, remove_halo=False, edgetaping=False, prefiltering=False,
                 discard_saturation=False, multichannel_kernel=False, method='fft', device=None, **extras):
         if self.patch_decomposition:
-            if wants_grad(images) or any(check_param(t, n, images) is not None for n, t in (("c", c), ("b", b), ("alpha", alpha), ("beta", beta))):
+            under_grad = wants_grad(images) or any(check_param(t, n, images) is not None for n, t in (("c", c), ("b", b), ("alpha", alpha), ("beta", beta)))
+            if under_grad and not is_rocm_float32(images):    # (float32 ROCm images take the differentiable branch: DESIGN.md 4.17)
                 refuse_under_grad("PolyblurDeblurring(patch_decomposition=True)", "the patch extraction and the windowed overlap-add "
                                   "(pb_extract_patches, pb_overlap_add) are not differentiated")
             return _patchwise_deblurring(images, self.patch_size, self.patch_overlap, self.batch_size,
@@ -382,7 +375,7 @@ class PolyblurDeblurring(_Base):
                                               discard_saturation=discard_saturation,
                                               multichannel_kernel=multichannel_kernel, method=method, q=q,
                                               n_angles=n_angles, n_interpolated_angles=n_interpolated_angles, **extras),
-                                         device=device)
+                                         device=device, under_grad=under_grad)
         return polyblur_deblurring(images, n_iter=n_iter, c=c, b=b, alpha=alpha, beta=beta, ker_size=ker_size,
                                    sigma_s=sigma_s, sigma_r=sigma_r, remove_halo=remove_halo, edgetaping=edgetaping,
                                    prefiltering=prefiltering, discard_saturation=discard_saturation,

@@ -495,6 +495,24 @@ class Engine:
         self._check(self.lib.pb_overlap_add(self.ctx, patches_ptr, out_ptr, dtype, B, Cc, H, W, g["ph"], g["pw"], g["step_h"], g["step_w"],
                                             g["n_i"], g["n_j"], g["pad_top"], g["pad_left"], C.c_void_p(wy_ptr), C.c_void_p(wx_ptr)))
 
+    def extract_patches_backward_ptr(self, grad_patches_ptr: int, grad_img_ptr: int, shape, grid: dict):
+        """d loss / d image of extract_patches_ptr over all n_i * n_j patches ([n*B + b] layout), float32
+        (pb_extract_patches_backward); grad_img is written, not accumulated; asynchronous"""
+        B, Cc, H, W = (int(v) for v in shape)
+        g = grid
+        self._check(self.lib.pb_extract_patches_backward(self.ctx, grad_patches_ptr, grad_img_ptr, B, Cc, H, W, g["ph"], g["pw"],
+                                                         g["step_h"], g["step_w"], g["n_i"], g["n_j"], g["pad_top"], g["pad_left"]))
+
+    def overlap_add_backward_ptr(self, patches_ptr: int, grad_out_ptr: int, grad_patches_ptr: int, shape, grid: dict, wy_ptr: int,
+                                 wx_ptr: int):
+        """d loss / d patches of overlap_add_ptr, float32 (pb_overlap_add_backward): the clamp passes the gradient where the
+        forward's value lies in [0, 1], both ends included; grad_patches is written everywhere and aliases no input; asynchronous"""
+        B, Cc, H, W = (int(v) for v in shape)
+        g = grid
+        self._check(self.lib.pb_overlap_add_backward(self.ctx, patches_ptr, grad_out_ptr, grad_patches_ptr, B, Cc, H, W, g["ph"], g["pw"],
+                                                     g["step_h"], g["step_w"], g["n_i"], g["n_j"], g["pad_top"], g["pad_left"],
+                                                     C.c_void_p(wy_ptr), C.c_void_p(wx_ptr)))
+
     def profile_begin(self):
         self._check(self.lib.pb_profile_begin(self.ctx))
 
